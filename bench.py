@@ -14,8 +14,13 @@ fp32 on CDNA4 has no MFMA; the default engine is bf16x2v — split-bf16
 emulation on the 2.5 PF bf16 matrix cores with the in-kernel second-best
 margin + exact-fp32 rescan that makes the argmin provably fp32-exact
 (tests/test_gpu_kernels.py). --fp32-mode native uses rocBLAS SGEMM (157 TF
-vector ALU) for comparison; --check measures assignment agreement vs the
-native engine over ALL local rows.
+vector ALU) for comparison.
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the steps, optionally --dump-outputs, print the JSON line. --full adds the
+secondary measurements: the pairwise-L2 Gdist/s figure (skip it with
+--no-pairwise) and, with --check, the assignment agreement vs the native
+engine over ALL local rows.
 """
 from __future__ import annotations
 
@@ -44,11 +49,34 @@ def parse_args():
                         "rescan) — exact fp32 argmin either way")
     p.add_argument("--chunk-rows", type=int, default=262144)
     p.add_argument("--seed", type=int, default=42)
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements (pairwise-L2 "
+                        "Gdist/s; --check) after the timed steps")
     p.add_argument("--check", action="store_true",
-                   help="cross-check final inertia vs native-fp32 assignment")
+                   help="with --full: cross-check the final assignment vs "
+                        "the native-fp32 engine")
     p.add_argument("--no-pairwise", action="store_true",
-                   help="skip the secondary pairwise-L2 Gdist/s measurement")
-    return p.parse_args()
+                   help="with --full: skip the secondary pairwise-L2 Gdist/s "
+                        "measurement")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed "
+                        "step returned (centroids, inertia) as DIR/<name>.npy")
+    args = p.parse_args()
+    if args.check and not args.full:
+        p.error("--check is part of the extended run: pass --full --check")
+    return args
+
+
+def dump_outputs(out_dir, centroids, inertia):
+    """Write the timed path's return values — the final centroids [k, dim]
+    (fp32) and the last step's inertia (scalar, fp64) — as .npy files."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "centroids.npy"),
+            centroids.detach().to("cpu", torch.float32).numpy())
+    np.save(os.path.join(out_dir, "inertia.npy"),
+            np.asarray(inertia, dtype=np.float64))
 
 
 def measure_pairwise_gdist(dev) -> float:
@@ -191,16 +219,20 @@ def main():
         },
     }
 
-    if args.check and use_gpu:
+    if args.dump_outputs and rank == 0:
+        # centroids/inertia are already allreduced: identical on every rank
+        dump_outputs(args.dump_outputs, c, inertia)
+
+    if args.full and args.check and use_gpu:
         # assignment agreement between emulated and native fp32 engines
         d_emul, a_emul = fused_l2nn(x, c, fp32_mode=args.fp32_mode)
         d_nat, a_nat = fused_l2nn(x, c, fp32_mode="native")
         agree = float((a_emul == a_nat).float().mean().item())
         result["config"]["assign_agreement_vs_native_fp32"] = agree
 
-    if use_gpu and rank == 0 and not args.no_pairwise:
+    if args.full and use_gpu and rank == 0 and not args.no_pairwise:
         # secondary metric: the pairwise half of BASELINE's
-        # headline, measured in the same driver-run process
+        # headline, measured in the same process as the flagship
         try:
             gd = measure_pairwise_gdist(device)
             result["config"]["pairwise_l2_1Mx128_fp32_gdist_per_s"] = round(gd, 1)

@@ -73,7 +73,9 @@ class TestDeviceNdarray:
         a = np.arange(6, dtype=np.int32).reshape(2, 3)
         d = device_ndarray(a)
         t = torch.from_dlpack(d)
-        np.testing.assert_array_equal(t.numpy(), a)
+        # device_ndarray(np) lands on the GPU when there is one
+        assert t.device == d.torch.device
+        np.testing.assert_array_equal(t.cpu().numpy(), a)
 
 
 class TestSerialize:
@@ -386,7 +388,11 @@ class TestLoggerEnvSinks:
             "log.info('should-appear')\n"
             "log.debug('should-not-appear')\n"
         )
-        r = subprocess.run([_sys.executable, "-c", code], env={
+        import os as _os
+        root = _os.path.dirname(_os.path.dirname(_os.path.abspath(__file__)))
+        # cwd = repository root: `python -c` imports raft_amd from the cwd,
+        # wherever pytest itself was started
+        r = subprocess.run([_sys.executable, "-c", code], cwd=root, env={
             **__import__("os").environ,
             "RAFT_AMD_DEBUG": str(f), "RAFT_AMD_LOG_LEVEL": "info"},
             capture_output=True, timeout=120)
@@ -419,7 +425,9 @@ class TestDeviceNdarraySurface:
         b = device_ndarray.empty((2, 2), dtype=np.float64)
         assert b.torch.dtype == torch.float64
         c = device_ndarray(np.arange(6, dtype=np.int32).reshape(2, 3))
-        assert torch.equal(c.torch, torch.arange(6, dtype=torch.int32).reshape(2, 3))
+        # c lives on the GPU when there is one: compare on its device
+        assert torch.equal(c.torch, torch.arange(6, dtype=torch.int32,
+                                                 device=c.torch.device).reshape(2, 3))
         # numpy round trip preserves values and dtype
         back = np.asarray(c.copy_to_host() if hasattr(c, "copy_to_host")
                           else c.torch.cpu().numpy())
