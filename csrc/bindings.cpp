@@ -52,6 +52,8 @@ void launch_row_normalize_l2(const float*, float*, long long, long long, float, 
 void launch_l2_epilogue(float*, const float*, const float*, long long, long long, hipStream_t);
 void launch_l2nn_epilogue(const float*, const float*, const float*, float*, int*,
                           long long, long long, hipStream_t);
+void launch_pairwise_expanded_epilogue(float*, const float*, const float*, long long,
+                                       long long, int, float, hipStream_t);
 void launch_pairwise_unexpanded(const float*, const float*, float*, long long, long long,
                                 long long, int, float, hipStream_t);
 // from rng.hip
@@ -237,6 +239,29 @@ torch::Tensor pairwise_unexpanded(torch::Tensor x, torch::Tensor y, int64_t code
                                        out.data_ptr<float>(), x.size(0), y.size(0),
                                        x.size(1), (int)code, (float)p, cur_stream());
   return out;
+}
+
+torch::Tensor pairwise_expanded_epilogue_(torch::Tensor g, torch::Tensor xa,
+                                         torch::Tensor ya, int64_t code, double d) {
+  check_f32_2d(g, "g");
+  TORCH_CHECK(g.scalar_type() == torch::kFloat32, "g must be float32");
+  TORCH_CHECK(code >= 0 && code <= 3, "bad expanded-epilogue code ", code);
+  const bool norms = code >= 2;  // Jaccard / Dice read the row norms
+  for (const auto* t : {&xa, &ya}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == g.device(), "xa/ya must be on g's device");
+    TORCH_CHECK(t->scalar_type() == torch::kFloat32, "xa/ya must be float32");
+    TORCH_CHECK(t->dim() == 1 && t->is_contiguous(), "xa/ya must be contiguous 1-D");
+  }
+  if (norms) {
+    TORCH_CHECK(xa.size(0) == g.size(0), "xa must have g.size(0) entries");
+    TORCH_CHECK(ya.size(0) == g.size(1), "ya must have g.size(1) entries");
+  }
+  if (code == 1) TORCH_CHECK(d > 0, "Russel-Rao needs d > 0");
+  raft_amd::launch_pairwise_expanded_epilogue(
+      g.data_ptr<float>(), norms ? xa.data_ptr<float>() : nullptr,
+      norms ? ya.data_ptr<float>() : nullptr, g.size(0), g.size(1), (int)code,
+      (float)d, cur_stream());
+  return g;
 }
 
 torch::Tensor rng_uniform(int64_t n, int64_t seed, int64_t subseq, int64_t device,
@@ -834,6 +859,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("l2_epilogue_", &l2_epilogue_, "in-place L2 distance epilogue");
   m.def("l2nn_epilogue", &l2nn_epilogue, "fused argmin epilogue over GEMM tile");
   m.def("pairwise_unexpanded", &pairwise_unexpanded, "tiled unexpanded distances");
+  m.def("pairwise_expanded_epilogue_", &pairwise_expanded_epilogue_,
+        "in-place Hellinger/Russel-Rao/Jaccard/Dice epilogue over a GEMM result");
   m.def("rng_uniform", &rng_uniform, "counter-based uniform [0,1)",
         pybind11::arg("n"), pybind11::arg("seed"), pybind11::arg("subseq"),
         pybind11::arg("device"), pybind11::arg("gen") = 0);

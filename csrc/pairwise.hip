@@ -156,6 +156,10 @@ __global__ void pairwise_unexp_kernel(const float* __restrict__ x, const float* 
   }
 }
 
+// codes 5..8 (KL, Jensen-Shannon, Bray-Curtis, Haversine): pairwise_metrics.hip
+void launch_pairwise_metrics(const float* x, const float* y, float* out, long long m,
+                             long long n, long long d, int code, hipStream_t stream);
+
 void launch_pairwise_unexpanded(const float* x, const float* y, float* out,
                                 long long m, long long n, long long d, int code,
                                 float p, hipStream_t stream) {
@@ -167,6 +171,8 @@ void launch_pairwise_unexpanded(const float* x, const float* y, float* out,
     case 2: hipLaunchKernelGGL((pairwise_unexp_kernel<2>), grid, block, 0, stream, x, y, out, m, n, d, p); break;
     case 3: hipLaunchKernelGGL((pairwise_unexp_kernel<3>), grid, block, 0, stream, x, y, out, m, n, d, p); break;
     case 4: hipLaunchKernelGGL((pairwise_unexp_kernel<4>), grid, block, 0, stream, x, y, out, m, n, d, p); break;
+    case 5: case 6: case 7: case 8:
+      launch_pairwise_metrics(x, y, out, m, n, d, code, stream); break;
     default: throw std::runtime_error("bad pairwise code");
   }
 }

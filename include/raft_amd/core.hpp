@@ -17,6 +17,12 @@ enum class ReduceOpCode : int {
 // unexpanded pairwise-distance codes (launch_pairwise_unexpanded)
 enum class DistanceCode : int {
   kL1 = 0, kLinf = 1, kLp = 2, kCanberra = 3, kHamming = 4,
+  kKLDivergence = 5, kJensenShannon = 6, kBrayCurtis = 7, kHaversine = 8,
+};
+
+// expanded-form epilogue codes (launch_pairwise_expanded_epilogue)
+enum class ExpandedDistanceCode : int {
+  kHellinger = 0, kRusselRao = 1, kJaccard = 2, kDice = 3,
 };
 
 }  // namespace raft_amd

@@ -1,4 +1,5 @@
-// Pairwise distances (csrc/pairwise.hip, csrc/pairwise_mfma.hip).
+// Pairwise distances (csrc/pairwise.hip, csrc/pairwise_metrics.hip,
+// csrc/pairwise_mfma.hip).
 // The fp32 L2 path runs as split-bf16 slice products on MFMA (no fp32 MFMA
 // on CDNA4): xsl/csl are nslice in {1,2,3} bf16 slice pointers.
 #pragma once
@@ -14,6 +15,13 @@ void launch_l2nn_epilogue(const float* g, const float* xn, const float* yn,
 // code = DistanceCode
 void launch_pairwise_unexpanded(const float* x, const float* y, float* out, long long m,
                                 long long n, long long d, int code, float p, hipStream_t s);
+// in-place expanded-form epilogue over a GEMM result g[m,n] = <x_i, y_j>
+// (csrc/pairwise_metrics.hip); code = ExpandedDistanceCode, d = feature
+// count (Russel-Rao). xa[m]/ya[n] = squared row norms, read by Jaccard and
+// Dice only (may be null for Hellinger / Russel-Rao)
+void launch_pairwise_expanded_epilogue(float* g, const float* xa, const float* ya,
+                                       long long m, long long n, int code, float d,
+                                       hipStream_t s);
 // 128x128-tile MFMA kernel; out[ldo] row stride; epilogue fused into the
 // single non-temporal C write
 void launch_pairwise_l2_mfma(const void** xsl, const void** csl, const float* xn,

@@ -95,6 +95,7 @@ inline void select_k(device_matrix_view<const float> in,
 }
 
 // ---- pairwise distance (unexpanded metrics) -------------------------------
+// kHaversine takes [lat, lon] rows (extent(1) == 2)
 inline void pairwise_distance(device_matrix_view<const float> x,
                               device_matrix_view<const float> y,
                               device_matrix_view<float> out, DistanceCode code,
@@ -105,6 +106,26 @@ inline void pairwise_distance(device_matrix_view<const float> x,
   launch_pairwise_unexpanded(x.data_handle(), y.data_handle(),
                              out.data_handle(), x.extent(0), y.extent(0),
                              x.extent(1), static_cast<int>(code), p, stream);
+}
+
+// ---- expanded-form epilogue (Hellinger / Russel-Rao / Jaccard / Dice) -----
+// in place over g[m, n] = <x_i, y_j>; xa[m] / ya[n] are the squared row norms
+// (required for kJaccard and kDice; ignored, and may be empty, otherwise);
+// d is the feature count (kRusselRao)
+inline void pairwise_expanded_epilogue(device_matrix_view<float> g,
+                                       device_vector_view<const float> xa,
+                                       device_vector_view<const float> ya,
+                                       ExpandedDistanceCode code, float d,
+                                       hipStream_t stream = nullptr) {
+  const bool norms = code == ExpandedDistanceCode::kJaccard ||
+                     code == ExpandedDistanceCode::kDice;
+  if (norms && (xa.extent(0) != g.extent(0) || ya.extent(0) != g.extent(1)))
+    throw std::invalid_argument("pairwise_expanded_epilogue: extents mismatch");
+  if (code == ExpandedDistanceCode::kRusselRao && !(d > 0.f))
+    throw std::invalid_argument("pairwise_expanded_epilogue: d must be > 0");
+  launch_pairwise_expanded_epilogue(g.data_handle(), xa.data_handle(),
+                                    ya.data_handle(), g.extent(0), g.extent(1),
+                                    static_cast<int>(code), d, stream);
 }
 
 // ---- row reductions -------------------------------------------------------
