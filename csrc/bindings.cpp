@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <c10/hip/HIPStream.h>
 
+#include <limits>
+
 namespace raft_amd {
 
 // from rng.hip (device sampling test driver)
@@ -129,6 +131,16 @@ void launch_pairwise_l2_filter(const void**, const void**, const float*, const f
 void launch_pairwise_l2_filter256(const void**, const void**, const float*, const float*,
                                   const float*, float*, int*, int*, int, long long,
                                   long long, long long, int, int, hipStream_t);
+void launch_eps_neighbors_l2sq(const void**, const void**, const float*, const float*,
+                               const float*, const float*, unsigned int*,
+                               unsigned long long*, float, float, float, long long,
+                               long long, int, int, long long, int, hipStream_t);
+void launch_bitmap_row_degrees(const unsigned int*, long long*, long long, long long,
+                               hipStream_t);
+void launch_bitmap_rows_to_csr(const unsigned int*, const long long*, int*, long long,
+                               long long, hipStream_t);
+void launch_bitmap_rows_expand(const unsigned int*, bool*, long long, long long,
+                               long long, hipStream_t);
 // from gemm_rocblas.cpp
 void gemm_bf16_f32_rowmajor(const void*, const void*, float*, long long, long long,
                             long long, float, void*);
@@ -659,6 +671,118 @@ void pairwise_l2_filter(std::vector<torch::Tensor> x_slices,
   }
 }
 
+const unsigned int* bitmap_words(const torch::Tensor& bm, const char* who) {
+  TORCH_CHECK(bm.is_cuda() && bm.scalar_type() == torch::kInt32 && bm.dim() == 2 &&
+              bm.is_contiguous(), who, ": bitmap must be a contiguous int32 [m, words] GPU tensor");
+  return reinterpret_cast<const unsigned int*>(bm.data_ptr<int>());
+}
+
+// packed eps-neighborhood bitmap of one row block (fills `bitmap` in place).
+// xf/yf present -> verified fp32 engine (exact recheck of the band pairs,
+// counted into `rechecked`); absent -> single bf16 slice decided by the score.
+void eps_neighbors_l2sq(std::vector<torch::Tensor> x_slices,
+                        std::vector<torch::Tensor> y_slices, torch::Tensor xn,
+                        torch::Tensor yn, c10::optional<torch::Tensor> xf,
+                        c10::optional<torch::Tensor> yf, torch::Tensor bitmap,
+                        c10::optional<torch::Tensor> rechecked, int64_t n_cols,
+                        double eps_sq, double lead, double tail) {
+  const int nslice = (int)x_slices.size();
+  TORCH_CHECK(nslice >= 1 && nslice <= 2 && y_slices.size() == x_slices.size(),
+              "eps_neighbors_l2sq: 1 or 2 slices");
+  const void* xsl[3];
+  const void* csl[3];
+  for (int s = 0; s < nslice; s++) {
+    TORCH_CHECK(x_slices[s].is_cuda() && x_slices[s].scalar_type() == torch::kBFloat16
+                && x_slices[s].is_contiguous() && x_slices[s].dim() == 2);
+    TORCH_CHECK(y_slices[s].is_cuda() && y_slices[s].scalar_type() == torch::kBFloat16
+                && y_slices[s].is_contiguous() && y_slices[s].dim() == 2);
+    TORCH_CHECK(x_slices[s].sizes() == x_slices[0].sizes() &&
+                y_slices[s].sizes() == y_slices[0].sizes());
+    xsl[s] = x_slices[s].data_ptr();
+    csl[s] = y_slices[s].data_ptr();
+  }
+  const long long m = x_slices[0].size(0);
+  const long long n = y_slices[0].size(0);
+  const long long d = x_slices[0].size(1);
+  TORCH_CHECK(n == n_cols, "eps_neighbors_l2sq: y slices must have n_cols rows");
+  TORCH_CHECK(d % 64 == 0 && y_slices[0].size(1) == d,
+              "eps_neighbors_l2sq: d must be a multiple of 64 and equal for x and y");
+  TORCH_CHECK(n < (1ll << 31) && m < (1ll << 31), "eps_neighbors_l2sq: m, n < 2^31");
+  TORCH_CHECK(xn.is_cuda() && xn.scalar_type() == torch::kFloat32 && xn.is_contiguous()
+              && xn.numel() == m);
+  TORCH_CHECK(yn.is_cuda() && yn.scalar_type() == torch::kFloat32 && yn.is_contiguous()
+              && yn.numel() == n);
+  const float eps2 = (float)eps_sq;
+  TORCH_CHECK(eps2 >= 0.f && eps2 <= std::numeric_limits<float>::max(),
+              "eps_neighbors_l2sq: eps_sq must be finite and >= 0");
+  const long long n_words = (n + 31) / 32;
+  unsigned int* bm = const_cast<unsigned int*>(bitmap_words(bitmap, "eps_neighbors_l2sq"));
+  TORCH_CHECK(bitmap.size(0) == m && bitmap.size(1) == n_words,
+              "eps_neighbors_l2sq: bitmap must be [m, ceil(n/32)]");
+  const float* xfp = nullptr;
+  const float* yfp = nullptr;
+  unsigned long long* cnt = nullptr;
+  long long df = d;
+  TORCH_CHECK(xf.has_value() == yf.has_value());
+  if (xf.has_value()) {
+    check_f32_2d(xf.value(), "xf");
+    check_f32_2d(yf.value(), "yf");
+    TORCH_CHECK(xf.value().scalar_type() == torch::kFloat32 &&
+                yf.value().scalar_type() == torch::kFloat32);
+    df = xf.value().size(1);
+    TORCH_CHECK(xf.value().size(0) == m && yf.value().size(0) == n &&
+                yf.value().size(1) == df && df <= d,
+                "eps_neighbors_l2sq: xf/yf shapes must match the slices");
+    TORCH_CHECK(rechecked.has_value() && rechecked.value().is_cuda() &&
+                rechecked.value().scalar_type() == torch::kInt64 &&
+                rechecked.value().numel() >= 1,
+                "eps_neighbors_l2sq: the verified engine needs an int64 counter");
+    xfp = xf.value().data_ptr<float>();
+    yfp = yf.value().data_ptr<float>();
+    cnt = reinterpret_cast<unsigned long long*>(rechecked.value().data_ptr<int64_t>());
+  } else {
+    TORCH_CHECK(nslice == 1, "eps_neighbors_l2sq: 2 slices need the fp32 recheck");
+  }
+  raft_amd::launch_eps_neighbors_l2sq(xsl, csl, xn.data_ptr<float>(),
+                                      yn.data_ptr<float>(), xfp, yfp, bm, cnt, eps2,
+                                      (float)lead, (float)tail, m, n, (int)d, (int)df,
+                                      n_words, nslice, cur_stream());
+}
+
+void bitmap_row_degrees(torch::Tensor bitmap, torch::Tensor deg) {
+  const unsigned int* bm = bitmap_words(bitmap, "bitmap_row_degrees");
+  TORCH_CHECK(deg.is_cuda() && deg.scalar_type() == torch::kInt64 &&
+              deg.is_contiguous() && deg.numel() == bitmap.size(0));
+  raft_amd::launch_bitmap_row_degrees(bm, reinterpret_cast<long long*>(deg.data_ptr<int64_t>()),
+                                      bitmap.size(0), bitmap.size(1), cur_stream());
+}
+
+void bitmap_rows_to_csr(torch::Tensor bitmap, torch::Tensor indptr,
+                        torch::Tensor indices) {
+  const unsigned int* bm = bitmap_words(bitmap, "bitmap_rows_to_csr");
+  TORCH_CHECK(indptr.is_cuda() && indptr.scalar_type() == torch::kInt64 &&
+              indptr.is_contiguous() && indptr.numel() == bitmap.size(0) + 1,
+              "bitmap_rows_to_csr: indptr must be int64 [m+1]");
+  TORCH_CHECK(indices.is_cuda() && indices.scalar_type() == torch::kInt32 &&
+              indices.is_contiguous() && indices.dim() == 1,
+              "bitmap_rows_to_csr: indices must be int32 [nnz]");
+  TORCH_CHECK(bitmap.size(1) < (1ll << 26), "bitmap_rows_to_csr: n must be < 2^31");
+  if (indices.numel() == 0) return;
+  raft_amd::launch_bitmap_rows_to_csr(
+      bm, reinterpret_cast<const long long*>(indptr.data_ptr<int64_t>()),
+      indices.data_ptr<int>(), bitmap.size(0), bitmap.size(1), cur_stream());
+}
+
+void bitmap_rows_expand(torch::Tensor bitmap, torch::Tensor out) {
+  const unsigned int* bm = bitmap_words(bitmap, "bitmap_rows_expand");
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == torch::kBool && out.dim() == 2 &&
+              out.is_contiguous() && out.size(0) == bitmap.size(0) &&
+              (out.size(1) + 31) / 32 == bitmap.size(1),
+              "bitmap_rows_expand: out must be bool [m, n] with ceil(n/32) words");
+  raft_amd::launch_bitmap_rows_expand(bm, out.data_ptr<bool>(), bitmap.size(0),
+                                      out.size(1), bitmap.size(1), cur_stream());
+}
+
 // backend toggle (reference parity: cublas vs cublasLt wrapper pair) —
 // RAFT_AMD_GEMM_BACKEND=hipblaslt routes the bf16->f32 GEMMs through the
 // hipBLASLt heuristic path (csrc/gemm_hipblaslt.cpp)
@@ -987,6 +1111,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("k"), pybind11::arg("select_min") = true);
   m.def("pairwise_l2_filter", &pairwise_l2_filter,
         "threshold-filtered pairwise L2 candidate emission (fused kNN)");
+  m.def("eps_neighbors_l2sq", &eps_neighbors_l2sq,
+        "verified eps-neighborhood (squared L2) packed adjacency bitmap",
+        pybind11::arg("x_slices"), pybind11::arg("y_slices"), pybind11::arg("xn"),
+        pybind11::arg("yn"), pybind11::arg("xf"), pybind11::arg("yf"),
+        pybind11::arg("bitmap"), pybind11::arg("rechecked"), pybind11::arg("n_cols"),
+        pybind11::arg("eps_sq"), pybind11::arg("lead") = 0x1p-13,
+        pybind11::arg("tail") = 0x1p-18);
+  m.def("bitmap_row_degrees", &bitmap_row_degrees,
+        "per-row popcount of a row-padded bitmap into an int64 vector");
+  m.def("bitmap_rows_to_csr", &bitmap_rows_to_csr,
+        "row-padded bitmap -> sorted int32 CSR column ids at indptr[row]");
+  m.def("bitmap_rows_expand", &bitmap_rows_expand,
+        "row-padded bitmap -> dense bool [m, n]");
   m.def("pairwise_l2_mfma", &pairwise_l2_mfma,
         "fused split-bf16 MFMA pairwise L2 tile (single-write epilogue)",
         pybind11::arg("x_slices"), pybind11::arg("y_slices"), pybind11::arg("xn"),

@@ -32,4 +32,27 @@ void launch_l2nn_verify_repair(const float* x, const float* c, const float* xn,
                                hipStream_t s, float lead = 0x1p-13f,
                                float tail = 0x1p-18f);
 
+// Verified epsilon-neighborhood (csrc/eps_neighbors.hip): packed adjacency
+// bitmap[i][j] = (||x_i - y_j||^2 <= eps2), n_words 32-bit words per row,
+// little-endian bits, tail bits zero. xsl/csl are bf16 slices padded to
+// d % 64 == 0. xf/yf (original fp32 rows, leading dim df) enable the exact
+// recheck of pairs within 2*(lead*sqrt(xn*yn) + tail*(xn+yn)) of eps2 and
+// require the `rechecked` counter; pass nullptr for bf16 input (1 slice).
+// eps2 must be finite and >= 0.
+void launch_eps_neighbors_l2sq(const void** xsl, const void** csl, const float* xn,
+                               const float* yn, const float* xf, const float* yf,
+                               unsigned int* bitmap, unsigned long long* rechecked,
+                               float eps2, float lead, float tail, long long m,
+                               long long n, int d, int df, long long n_words,
+                               int nslice, hipStream_t s);
+// row-padded bitmap utilities: per-row popcount, CSR fill (sorted int32
+// column ids at indptr[row]) and dense bool expansion
+void launch_bitmap_row_degrees(const unsigned int* bitmap, long long* deg,
+                               long long m, long long n_words, hipStream_t s);
+void launch_bitmap_rows_to_csr(const unsigned int* bitmap, const long long* indptr,
+                               int* indices, long long m, long long n_words,
+                               hipStream_t s);
+void launch_bitmap_rows_expand(const unsigned int* bitmap, bool* out, long long m,
+                               long long n, long long n_words, hipStream_t s);
+
 }  // namespace raft_amd
