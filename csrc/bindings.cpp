@@ -141,6 +141,16 @@ void launch_bitmap_rows_to_csr(const unsigned int*, const long long*, int*, long
                                long long, hipStream_t);
 void launch_bitmap_rows_expand(const unsigned int*, bool*, long long, long long,
                                long long, hipStream_t);
+void launch_masked_l2nn(const void**, const void**, const float*, const float*,
+                        const int*, const unsigned int*, long long, const int*, float*,
+                        float*, int*, float*, int*, float*, unsigned long long*,
+                        long long, int, int, int, int, hipStream_t);
+void launch_masked_l2nn_verify_repair(const float*, const float*, const float*,
+                                      const int*, const unsigned int*, long long,
+                                      const int*, const int*, const int*, float*, int*,
+                                      const float*, const float*, int*, unsigned int*,
+                                      unsigned long long*, unsigned long long*,
+                                      long long, int, int, float, float, hipStream_t);
 // from gemm_rocblas.cpp
 void gemm_bf16_f32_rowmajor(const void*, const void*, float*, long long, long long,
                             long long, float, void*);
@@ -749,6 +759,157 @@ void eps_neighbors_l2sq(std::vector<torch::Tensor> x_slices,
                                       n_words, nslice, cur_stream());
 }
 
+static const int* masked_nn_i32(const c10::optional<torch::Tensor>& t, long long numel,
+                                const char* what) {
+  if (!t.has_value()) return nullptr;
+  TORCH_CHECK(t.value().is_cuda() && t.value().scalar_type() == torch::kInt32 &&
+              t.value().is_contiguous() && t.value().numel() == numel,
+              "masked_l2nn: ", what, " must be a contiguous int32 GPU vector of ",
+              numel, " elements");
+  return t.value().data_ptr<int>();
+}
+
+static const unsigned int* masked_nn_adj(const c10::optional<torch::Tensor>& adj,
+                                         long long m, long long n_groups,
+                                         long long* words) {
+  *words = 0;
+  if (!adj.has_value()) return nullptr;
+  const unsigned int* p = bitmap_words(adj.value(), "masked_l2nn");
+  TORCH_CHECK(adj.value().size(0) == m && adj.value().size(1) == (n_groups + 31) / 32,
+              "masked_l2nn: adj must be [m, ceil(n_groups/32)]");
+  *words = adj.value().size(1);
+  return p;
+}
+
+// masked fused L2-NN over one row block. y_group holds ids in [0, n_groups),
+// non-decreasing (the Python layer builds it from the group offsets). scratch
+// is float32 [3, n_split, m]: the per-split partial (best, second, index).
+// counters is int64 [2]: visited and skipped tiles are ADDED to it.
+std::vector<torch::Tensor> masked_l2nn(std::vector<torch::Tensor> x_slices,
+                                       std::vector<torch::Tensor> y_slices,
+                                       torch::Tensor xn, torch::Tensor yn,
+                                       torch::Tensor y_group, int64_t n_groups,
+                                       c10::optional<torch::Tensor> adj,
+                                       c10::optional<torch::Tensor> x_group,
+                                       torch::Tensor scratch, torch::Tensor counters) {
+  const int nslice = (int)x_slices.size();
+  TORCH_CHECK(nslice >= 1 && nslice <= 2 && y_slices.size() == x_slices.size(),
+              "masked_l2nn: 1 or 2 slices");
+  const void* xsl[3];
+  const void* csl[3];
+  for (int s = 0; s < nslice; s++) {
+    TORCH_CHECK(x_slices[s].is_cuda() && x_slices[s].scalar_type() == torch::kBFloat16
+                && x_slices[s].is_contiguous() && x_slices[s].dim() == 2);
+    TORCH_CHECK(y_slices[s].is_cuda() && y_slices[s].scalar_type() == torch::kBFloat16
+                && y_slices[s].is_contiguous() && y_slices[s].dim() == 2);
+    TORCH_CHECK(x_slices[s].sizes() == x_slices[0].sizes() &&
+                y_slices[s].sizes() == y_slices[0].sizes());
+    xsl[s] = x_slices[s].data_ptr();
+    csl[s] = y_slices[s].data_ptr();
+  }
+  const long long m = x_slices[0].size(0);
+  const long long n = y_slices[0].size(0);
+  const long long d = x_slices[0].size(1);
+  TORCH_CHECK(m >= 1 && n >= 1, "masked_l2nn: empty inputs are handled by the caller");
+  TORCH_CHECK(d % 64 == 0 && d > 0 && y_slices[0].size(1) == d,
+              "masked_l2nn: d must be a multiple of 64 and equal for x and y");
+  TORCH_CHECK(n < (1ll << 31) - 128 && m < (1ll << 31), "masked_l2nn: m, n < 2^31");
+  TORCH_CHECK(xn.is_cuda() && xn.scalar_type() == torch::kFloat32 && xn.is_contiguous()
+              && xn.numel() == m);
+  TORCH_CHECK(yn.is_cuda() && yn.scalar_type() == torch::kFloat32 && yn.is_contiguous()
+              && yn.numel() == n);
+  TORCH_CHECK(n_groups >= 1 && n_groups < (1ll << 31), "masked_l2nn: n_groups >= 1");
+  const int* yg = masked_nn_i32(y_group, n, "y_group");
+  const int* xg = masked_nn_i32(x_group, m, "x_group");
+  long long adj_words = 0;
+  const unsigned int* ap = masked_nn_adj(adj, m, n_groups, &adj_words);
+  TORCH_CHECK(ap != nullptr || xg != nullptr, "masked_l2nn: adj or x_group is required");
+  TORCH_CHECK(scratch.is_cuda() && scratch.scalar_type() == torch::kFloat32 &&
+              scratch.is_contiguous() && scratch.dim() == 3 && scratch.size(0) == 3 &&
+              scratch.size(2) == m,
+              "masked_l2nn: scratch must be float32 [3, n_split, m]");
+  const long long n_split = scratch.size(1);
+  TORCH_CHECK(n_split >= 1 && n_split <= (n + 127) / 128,
+              "masked_l2nn: n_split must be in [1, ceil(n/128)]");
+  TORCH_CHECK(counters.is_cuda() && counters.scalar_type() == torch::kInt64 &&
+              counters.is_contiguous() && counters.numel() == 2,
+              "masked_l2nn: counters must be int64 [2]");
+  float* pd = scratch.data_ptr<float>();
+  float* pd2 = pd + n_split * m;
+  int* pi = reinterpret_cast<int*>(pd + 2 * n_split * m);
+  auto dmin = torch::empty({(int64_t)m}, xn.options());
+  auto dmin2 = torch::empty({(int64_t)m}, xn.options());
+  auto amin = torch::empty({(int64_t)m}, xn.options().dtype(torch::kInt32));
+  raft_amd::launch_masked_l2nn(
+      xsl, csl, xn.data_ptr<float>(), yn.data_ptr<float>(), yg, ap, adj_words, xg, pd,
+      pd2, pi, dmin.data_ptr<float>(), amin.data_ptr<int>(), dmin2.data_ptr<float>(),
+      reinterpret_cast<unsigned long long*>(counters.data_ptr<int64_t>()), m, (int)n,
+      (int)d, (int)n_split, nslice, cur_stream());
+  return {dmin, amin, dmin2};
+}
+
+// exact fp32 verify / repair of a masked_l2nn result, in place. y_group is
+// the int32 [n] group id of every y row (ids in [0, n_groups)); y_rank
+// (optional int32 [n] permutation of 0..n-1) replaces the column index in the
+// exact-tie rule of the rescan.
+void masked_l2nn_verify_repair(torch::Tensor x, torch::Tensor y, torch::Tensor xn,
+                               torch::Tensor y_group, int64_t n_groups,
+                               c10::optional<torch::Tensor> adj,
+                               c10::optional<torch::Tensor> x_group,
+                               c10::optional<torch::Tensor> y_rank, torch::Tensor dmin,
+                               torch::Tensor amin, torch::Tensor dmin2,
+                               torch::Tensor yn_max, torch::Tensor rescanned,
+                               double lead, double tail) {
+  check_f32_2d(x, "x");
+  check_f32_2d(y, "y");
+  const long long m = x.size(0), n = y.size(0), df = x.size(1);
+  TORCH_CHECK(x.scalar_type() == torch::kFloat32 && y.scalar_type() == torch::kFloat32 &&
+              y.size(1) == df && df >= 1, "masked_l2nn_verify_repair: x, y fp32 [*, d]");
+  TORCH_CHECK(m >= 1 && m < (1ll << 31) && n >= 1 && n < (1ll << 31) - 2048 &&
+              df < (1ll << 31), "masked_l2nn_verify_repair: 1 <= m, n < 2^31");
+  TORCH_CHECK(n_groups >= 1, "masked_l2nn_verify_repair: at least one group");
+  const int* yg = masked_nn_i32(y_group, n, "y_group");
+  const int* xg = masked_nn_i32(x_group, m, "x_group");
+  const int* yr = masked_nn_i32(y_rank, n, "y_rank");
+  long long adj_words = 0;
+  const unsigned int* ap = masked_nn_adj(adj, m, n_groups, &adj_words);
+  TORCH_CHECK(ap != nullptr || xg != nullptr,
+              "masked_l2nn_verify_repair: adj or x_group is required");
+  for (const torch::Tensor* t : {&xn, &dmin, &dmin2})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kFloat32 &&
+                t->is_contiguous() && t->numel() == m,
+                "masked_l2nn_verify_repair: xn, dmin, dmin2 must be float32 [m]");
+  TORCH_CHECK(amin.is_cuda() && amin.scalar_type() == torch::kInt32 &&
+              amin.is_contiguous() && amin.numel() == m);
+  TORCH_CHECK(yn_max.is_cuda() && yn_max.scalar_type() == torch::kFloat32 &&
+              yn_max.numel() >= 1);
+  TORCH_CHECK(rescanned.is_cuda() && rescanned.scalar_type() == torch::kInt64 &&
+              rescanned.numel() >= 1,
+              "masked_l2nn_verify_repair: rescanned must be an int64 counter");
+  // rescan list, its length and the per-row (distance, key) minimum
+  auto i32 = xn.options().dtype(torch::kInt32);
+  auto rows = torch::empty({(int64_t)m}, i32);
+  auto count = torch::empty({1}, i32);
+  auto keys = torch::empty({(int64_t)m}, xn.options().dtype(torch::kInt64));
+  torch::Tensor inv;
+  const int* ivp = nullptr;
+  if (yr != nullptr) {
+    // rank -> column; an out-of-range rank fails here, not in the kernel
+    inv = torch::empty({(int64_t)n}, i32);
+    inv.index_put_({y_rank.value().to(torch::kInt64)},
+                   torch::arange((int64_t)n, i32));
+    ivp = inv.data_ptr<int>();
+  }
+  raft_amd::launch_masked_l2nn_verify_repair(
+      x.data_ptr<float>(), y.data_ptr<float>(), xn.data_ptr<float>(), yg, ap, adj_words,
+      xg, yr, ivp, dmin.data_ptr<float>(), amin.data_ptr<int>(), dmin2.data_ptr<float>(),
+      yn_max.data_ptr<float>(), rows.data_ptr<int>(),
+      reinterpret_cast<unsigned int*>(count.data_ptr<int>()),
+      reinterpret_cast<unsigned long long*>(keys.data_ptr<int64_t>()),
+      reinterpret_cast<unsigned long long*>(rescanned.data_ptr<int64_t>()), m, (int)n,
+      (int)df, (float)lead, (float)tail, cur_stream());
+}
+
 void bitmap_row_degrees(torch::Tensor bitmap, torch::Tensor deg) {
   const unsigned int* bm = bitmap_words(bitmap, "bitmap_row_degrees");
   TORCH_CHECK(deg.is_cuda() && deg.scalar_type() == torch::kInt64 &&
@@ -1118,6 +1279,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("bitmap"), pybind11::arg("rechecked"), pybind11::arg("n_cols"),
         pybind11::arg("eps_sq"), pybind11::arg("lead") = 0x1p-13,
         pybind11::arg("tail") = 0x1p-18);
+  m.def("masked_l2nn", &masked_l2nn,
+        "masked fused L2-NN (group mask, tile skip) -> (dmin, amin, dmin2)",
+        pybind11::arg("x_slices"), pybind11::arg("y_slices"), pybind11::arg("xn"),
+        pybind11::arg("yn"), pybind11::arg("y_group"), pybind11::arg("n_groups"),
+        pybind11::arg("adj"), pybind11::arg("x_group"), pybind11::arg("scratch"),
+        pybind11::arg("counters"));
+  m.def("masked_l2nn_verify_repair", &masked_l2nn_verify_repair,
+        "exact fp32 verify / repair of a masked L2-NN result (in place)",
+        pybind11::arg("x"), pybind11::arg("y"), pybind11::arg("xn"),
+        pybind11::arg("y_group"), pybind11::arg("n_groups"), pybind11::arg("adj"),
+        pybind11::arg("x_group"), pybind11::arg("y_rank"), pybind11::arg("dmin"), pybind11::arg("amin"),
+        pybind11::arg("dmin2"), pybind11::arg("yn_max"), pybind11::arg("rescanned"),
+        pybind11::arg("lead") = 0x1p-13, pybind11::arg("tail") = 0x1p-18);
   m.def("bitmap_row_degrees", &bitmap_row_degrees,
         "per-row popcount of a row-padded bitmap into an int64 vector");
   m.def("bitmap_rows_to_csr", &bitmap_rows_to_csr,

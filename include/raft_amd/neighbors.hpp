@@ -55,4 +55,41 @@ void launch_bitmap_rows_to_csr(const unsigned int* bitmap, const long long* indp
 void launch_bitmap_rows_expand(const unsigned int* bitmap, bool* out, long long m,
                                long long n, long long n_words, hipStream_t s);
 
+// Masked fused L2-NN (csrc/masked_l2nn.hip): per row of x the nearest y row
+// among the y GROUPS its mask allows. y_group[n] holds non-decreasing group
+// ids in [0, n_groups); a column of group g is allowed for row i iff
+// (adj == nullptr or bit g of adj row i is set) and g != x_group[i]
+// (x_group == nullptr excludes nothing; one of the two is required). adj has
+// adj_words 32-bit words per row. pd/pd2/pi are n_split * m scratch arrays
+// (one partial per column split, n_split in [1, ceil(n/128)]); visited and
+// skipped tiles are added to counters[0] and counters[1]. Writes the emulated
+// (dmin, amin, dmin2 = second best over allowed columns); rows with no
+// allowed column get (+inf, -1, +inf).
+void launch_masked_l2nn(const void** xsl, const void** csl, const float* xn,
+                        const float* yn, const int* y_group,
+                        const unsigned int* adj, long long adj_words,
+                        const int* x_group, float* pd, float* pd2, int* pi,
+                        float* dmin, int* amin, float* dmin2,
+                        unsigned long long* counters, long long m, int n, int d,
+                        int n_split, int nslice, hipStream_t s);
+// exact fp32 verify / repair of that result, in place and without a host
+// sync: rows with dmin2 - dmin <= 2*(lead*sqrt(xn*yn_max) + tail*(xn + yn_max))
+// rescan their allowed columns with the unexpanded fp32 distance (exact ties
+// to the smallest index, or to the smallest y_rank when given — then
+// inv_rank[y_rank[j]] == j is required too), every other row recomputes its
+// chosen distance. x/y have leading dimension df. Scratch: rescan_rows[m],
+// rescan_count[1] (zeroed here) and keys[m]. Rescanned rows are added to
+// *rescanned.
+void launch_masked_l2nn_verify_repair(const float* x, const float* y, const float* xn,
+                                      const int* y_group, const unsigned int* adj,
+                                      long long adj_words, const int* x_group,
+                                      const int* y_rank, const int* inv_rank,
+                                      float* dmin, int* amin, const float* dmin2,
+                                      const float* yn_max_dev, int* rescan_rows,
+                                      unsigned int* rescan_count,
+                                      unsigned long long* keys,
+                                      unsigned long long* rescanned, long long m,
+                                      int n, int df, float lead, float tail,
+                                      hipStream_t s);
+
 }  // namespace raft_amd

@@ -59,20 +59,7 @@ def mst(a, symmetrize: bool = True):
         is_min = cross & (wj == minw[cr])          # unique thanks to jitter
         sel = is_min.nonzero(as_tuple=True)[0]
         chosen[sel] = True
-        # (2) merge: each component's root points at its partner's root
-        parent = torch.arange(n, device=device)
-        parent[cr[sel]] = cc[sel]
-        # break 2-cycles a<->b: root at the smaller color id
-        two = parent[parent] == torch.arange(n, device=device)
-        parent = torch.where(two & (parent > torch.arange(n, device=device)),
-                             torch.arange(n, device=device), parent)
-        # (3) pointer-jump to fixpoint
-        for _ in range(64):
-            nxt = parent[parent]
-            if bool(torch.equal(nxt, parent)):
-                break
-            parent = nxt
-        color = parent[color]
+        color = merge_components(color, cr[sel], cc[sel])
 
     sel = chosen.nonzero(as_tuple=True)[0]
     u = torch.minimum(rows[sel], cols[sel])
@@ -81,6 +68,28 @@ def mst(a, symmetrize: bool = True):
     _, first_idx = _unique_first(key)
     keep = sel[first_idx]
     return rows[keep], cols[keep], w[keep].to(a.values.dtype)
+
+
+def merge_components(color: torch.Tensor, a: torch.Tensor, b: torch.Tensor):
+    """One Borůvka merge step: component a[i] joins component b[i] (both are
+    color ids, i.e. vertex ids of component roots). Returns the new color of
+    every vertex. The chosen edges must come from a strict total order on
+    the edges, so that the only cycles are 2-cycles a <-> b."""
+    n = color.numel()
+    ids = torch.arange(n, device=color.device)
+    # (2) merge: each component's root points at its partner's root
+    parent = ids.clone()
+    parent[a] = b
+    # break 2-cycles a<->b: root at the smaller color id
+    two = parent[parent] == ids
+    parent = torch.where(two & (parent > ids), ids, parent)
+    # (3) pointer-jump to fixpoint
+    for _ in range(64):
+        nxt = parent[parent]
+        if bool(torch.equal(nxt, parent)):
+            break
+        parent = nxt
+    return parent[color]
 
 
 def _unique_first(key: torch.Tensor):
