@@ -12,6 +12,8 @@
 
 #include <limits>
 
+#include "l2nn_engine.h"
+
 namespace raft_amd {
 
 // from rng.hip (device sampling test driver)
@@ -94,29 +96,6 @@ void launch_select_k_warpsort(const float*, float*, int*, long long, long long, 
 template <typename T>
 void launch_select_k_generic_t(const T*, const long long*, long long, long long,
                                T*, long long*, long long, long long, bool,
-                               hipStream_t);
-// from fused_l2nn.hip
-void launch_fused_l2nn_split(const void**, const void**, const float*, const float*,
-                             float*, int*, float*, long long, int, int, int,
-                             hipStream_t);
-// from fused_l2nn_2d.hip (XCD-swizzled tile-pair grid + partials combine)
-bool fused_l2nn_2d_supported(int nslice, long long m, int n, int d);
-void launch_fused_l2nn_2d(const void**, const void**, const float*, const float*,
-                          float*, float*, int*, float*, int*, float*,
-                          long long, int, int, int, hipStream_t);
-// from fused_l2nn_256.hip (256^2 counted-vmcnt double-buffered engine)
-bool fused_l2nn_256_supported(int nslice, long long m, int n, int d);
-void launch_fused_l2nn_256(const void**, const void**, const float*, const float*,
-                           float*, float*, int*, float*, int*, float*,
-                           long long, int, int, int, hipStream_t);
-// from fused_l2nn_v2.hip (persistent-X variant + w8 wide-tile variant)
-bool fused_l2nn_persist_supported(int nslice, int d);
-bool fused_l2nn_w8_supported(int nslice, int n, int d);
-void launch_fused_l2nn_w8(const void**, const void**, const float*, const float*,
-                          float*, int*, float*, long long, int, int, int,
-                          hipStream_t);
-void launch_fused_l2nn_persist(const void**, const void**, const float*, const float*,
-                               float*, int*, float*, long long, int, int, int,
                                hipStream_t);
 // from pairwise_mfma.hip
 void launch_pairwise_l2_mfma(const void**, const void**, const float*, const float*,
@@ -502,9 +481,40 @@ std::tuple<torch::Tensor, torch::Tensor> select_k(torch::Tensor x, int64_t k,
   return {vals, idx};
 }
 
+// "auto" -> Auto; an unknown name is an error, never a fallback
+static raft_amd::L2nnEngine l2nn_engine_arg(const std::string& engine) {
+  bool known;
+  const auto e = raft_amd::l2nn_engine_from_name(engine, &known);
+  TORCH_CHECK(known, "fused_l2nn: unknown engine '", engine, "'");
+  return e;
+}
+
+static raft_amd::L2nnPlan l2nn_plan(int64_t nslice, int64_t m, int64_t n, int64_t d,
+                                    const std::string& engine, int64_t gt) {
+  TORCH_CHECK(nslice >= 1 && nslice <= 3, "fused_l2nn: 1 to 3 slices");
+  TORCH_CHECK(n % 128 == 0, "fused_l2nn: n must be a multiple of 128");
+  TORCH_CHECK(d % 64 == 0, "fused_l2nn: d must be a multiple of 64");
+  TORCH_CHECK(gt == 0 || gt == 1 || gt == 2 || gt == 4 || gt == 8,
+              "fused_l2nn: gt must be 0 (default), 1, 2, 4 or 8");
+  auto plan = raft_amd::l2nn_resolve_engine((int)nslice, m, (int)n, (int)d,
+                                            l2nn_engine_arg(engine), (int)gt);
+  TORCH_CHECK(plan.error.empty(), plan.error, " (nslice=", nslice, ", m=", m,
+              ", n=", n, ", d=", d, ")");
+  return plan;
+}
+
+// (engine name, gt) that fused_l2nn_split runs for this shape and request
+std::tuple<std::string, int64_t> l2nn_resolve_engine(int64_t nslice, int64_t m,
+                                                     int64_t n, int64_t d,
+                                                     const std::string& engine,
+                                                     int64_t gt) {
+  const auto plan = l2nn_plan(nslice, m, n, d, engine, gt);
+  return {raft_amd::l2nn_engine_name(plan.engine), plan.gt};
+}
+
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> fused_l2nn_split(
     std::vector<torch::Tensor> x_slices, std::vector<torch::Tensor> c_slices,
-    torch::Tensor xn, torch::Tensor cn) {
+    torch::Tensor xn, torch::Tensor cn, const std::string& engine, int64_t gt) {
   const int nslice = (int)x_slices.size();
   TORCH_CHECK(nslice >= 1 && nslice <= 3 && c_slices.size() == x_slices.size());
   const void* xsl[3];
@@ -521,58 +531,21 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> fused_l2nn_split(
   const long long n = c_slices[0].size(0);
   const long long d = x_slices[0].size(1);
   TORCH_CHECK(c_slices[0].size(1) == d, "dim mismatch");
-  TORCH_CHECK(n % 128 == 0, "fused_l2nn: n must be a multiple of 128");
-  TORCH_CHECK(d % 64 == 0, "fused_l2nn: d must be a multiple of 64");
+  const auto plan = l2nn_plan(nslice, m, n, d, engine, gt);
   TORCH_CHECK(cn.numel() == n && xn.numel() == m);
   auto dmin = torch::empty({m}, xn.options());
   auto amin = torch::empty({m}, xn.options().dtype(torch::kInt32));
   auto dmin2 = torch::empty({m}, xn.options());
-  static const bool use_persist = [] {
-    const char* e = getenv("RAFT_AMD_PERSIST_L2NN");
-    return e && e[0] == '1';
-  }();  // measured slower than v1 at 10M x 256 (occupancy); kept for tuning
-  static const bool no_w8 = [] {
-    const char* e = getenv("RAFT_AMD_L2NN_W8");
-    return e && e[0] == '0';
-  }();
-  if (!use_persist && raft_amd::fused_l2nn_256_supported(nslice, m, (int)n, (int)d)) {
-    const long long n_col_tiles = n / 256;
-    auto pd = torch::empty({n_col_tiles * m}, xn.options());
-    auto pd2 = torch::empty({n_col_tiles * m}, xn.options());
-    auto pi = torch::empty({n_col_tiles * m}, xn.options().dtype(torch::kInt32));
-    raft_amd::launch_fused_l2nn_256(xsl, csl, xn.data_ptr<float>(),
-                                    cn.data_ptr<float>(), pd.data_ptr<float>(),
-                                    pd2.data_ptr<float>(), pi.data_ptr<int>(),
-                                    dmin.data_ptr<float>(), amin.data_ptr<int>(),
-                                    dmin2.data_ptr<float>(), m, (int)n, (int)d,
-                                    nslice, cur_stream());
-  } else if (!use_persist && raft_amd::fused_l2nn_2d_supported(nslice, m, (int)n, (int)d)) {
-    const long long n_col_tiles = n / 128;
-    auto pd = torch::empty({n_col_tiles * m}, xn.options());
-    auto pd2 = torch::empty({n_col_tiles * m}, xn.options());
-    auto pi = torch::empty({n_col_tiles * m}, xn.options().dtype(torch::kInt32));
-    raft_amd::launch_fused_l2nn_2d(xsl, csl, xn.data_ptr<float>(),
-                                   cn.data_ptr<float>(), pd.data_ptr<float>(),
-                                   pd2.data_ptr<float>(), pi.data_ptr<int>(),
-                                   dmin.data_ptr<float>(), amin.data_ptr<int>(),
-                                   dmin2.data_ptr<float>(), m, (int)n, (int)d,
-                                   nslice, cur_stream());
-  } else if (!no_w8 && !use_persist && raft_amd::fused_l2nn_w8_supported(nslice, (int)n, (int)d)) {
-    raft_amd::launch_fused_l2nn_w8(xsl, csl, xn.data_ptr<float>(),
-                                   cn.data_ptr<float>(), dmin.data_ptr<float>(),
-                                   amin.data_ptr<int>(), dmin2.data_ptr<float>(),
-                                   m, (int)n, (int)d, nslice, cur_stream());
-  } else if (use_persist && raft_amd::fused_l2nn_persist_supported(nslice, (int)d)) {
-    raft_amd::launch_fused_l2nn_persist(xsl, csl, xn.data_ptr<float>(),
-                                        cn.data_ptr<float>(), dmin.data_ptr<float>(),
-                                        amin.data_ptr<int>(), dmin2.data_ptr<float>(),
-                                        m, (int)n, (int)d, nslice, cur_stream());
-  } else {
-    raft_amd::launch_fused_l2nn_split(xsl, csl, xn.data_ptr<float>(),
-                                      cn.data_ptr<float>(), dmin.data_ptr<float>(),
-                                      amin.data_ptr<int>(), dmin2.data_ptr<float>(),
-                                      m, (int)n, (int)d, nslice, cur_stream());
-  }
+  // per-(row, col-tile group) partials of the 2d and 256 engines
+  auto pd = torch::empty({plan.n_groups * m}, xn.options());
+  auto pd2 = torch::empty({plan.n_groups * m}, xn.options());
+  auto pi = torch::empty({plan.n_groups * m}, xn.options().dtype(torch::kInt32));
+  raft_amd::launch_fused_l2nn(plan, xsl, csl, xn.data_ptr<float>(),
+                              cn.data_ptr<float>(), pd.data_ptr<float>(),
+                              pd2.data_ptr<float>(), pi.data_ptr<int>(),
+                              dmin.data_ptr<float>(), amin.data_ptr<int>(),
+                              dmin2.data_ptr<float>(), m, (int)n, (int)d, nslice,
+                              cur_stream());
   return {dmin, amin, dmin2};
 }
 
@@ -1310,7 +1283,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("lead") = 0x1p-13, pybind11::arg("tail") = 0x1p-18,
         "exact-fp32 verification/repair of split-bf16 L2-NN results");
   m.def("fused_l2nn_split", &fused_l2nn_split,
-        "fused split-bf16 MFMA L2-NN (distance + argmin, no materialization)");
+        "fused split-bf16 MFMA L2-NN (distance + argmin, no materialization); "
+        "engine names one kernel (csrc/l2nn_engine.h) and raises if it cannot "
+        "run the shape, gt = col-tiles per block of the 2d engines",
+        pybind11::arg("x_slices"), pybind11::arg("c_slices"), pybind11::arg("xn"),
+        pybind11::arg("cn"), pybind11::arg("engine") = "auto",
+        pybind11::arg("gt") = 0);
+  m.def("l2nn_resolve_engine", &l2nn_resolve_engine,
+        "(engine, gt) that fused_l2nn_split runs for a shape and request",
+        pybind11::arg("nslice"), pybind11::arg("m"), pybind11::arg("n"),
+        pybind11::arg("d"), pybind11::arg("engine") = "auto", pybind11::arg("gt") = 0);
   m.def("gemm_bf16_f32", &gemm_bf16_f32, "bf16 x bf16 -> f32 rocBLAS gemm_ex",
         pybind11::arg("a"), pybind11::arg("b"), pybind11::arg("out") = pybind11::none(),
         pybind11::arg("beta") = 0.0);

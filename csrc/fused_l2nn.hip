@@ -27,7 +27,8 @@
 
 #include <hip/hip_runtime.h>
 
-#include "mfma_common.h"
+#include "l2nn_engine.h"
+#include "l2nn_top2.h"
 
 namespace raft_amd {
 
@@ -69,10 +70,7 @@ __global__ void fused_l2nn_kernel(const __bf16* __restrict__ x0,
 
   float best[4][4], best2[4][4];
   int bidx[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; a++)
-#pragma unroll
-    for (int b = 0; b < 4; b++) { best[a][b] = INFINITY; best2[a][b] = INFINITY; bidx[a][b] = 0; }
+  top2_init(best, best2, bidx);
 
   const int n_tiles = n / 128;
 
@@ -95,71 +93,23 @@ __global__ void fused_l2nn_kernel(const __bf16* __restrict__ x0,
                               m - 1, n - 1, wr, wc, lane);
     }
 
-    // epilogue: fold this tile's columns into each lane's LOCAL running
-    // (best, second-best) — lanes own disjoint column sets, so no cross-lane
-    // work is needed per tile; ONE shuffle reduce happens after the nt loop
-    // (the per-tile 12-shuffle reduce was ~1/3 of the kernel's non-MFMA time).
-    const int col_base = nt * 128 + wc * 64;
-#pragma unroll
-    for (int fr = 0; fr < 4; fr++) {
-#pragma unroll
-      for (int reg = 0; reg < 4; reg++) {
-#pragma unroll
-        for (int fc = 0; fc < 4; fc++) {
-          const int col = col_base + fc * 16 + (lane & 15);
-          const float s = cn[col] - 2.f * acc[fr][fc][reg];
-          // second-best via one v_med3_f32 (invariant best <= best2)
-          best2[fr][reg] = __builtin_amdgcn_fmed3f(s, best[fr][reg],
-                                                   best2[fr][reg]);
-          if (s < best[fr][reg]) {
-            best[fr][reg] = s;
-            bidx[fr][reg] = col;
-          }
-        }
-      }
-    }
+    // lanes own disjoint column sets, so the per-tile fold is lane-local
+    top2_fold_tile(acc, cn, nt * 128 + wc * 64 + (lane & 15), best, best2, bidx);
   }
 
-  // ONE cross-lane top-2 reduce per (fr, reg) over the 16 lanes of the
-  // row-group (index-aware merge: shared-best lanes cannot donate their
-  // loser as a second-best candidate)
-#pragma unroll
-  for (int fr = 0; fr < 4; fr++) {
-#pragma unroll
-    for (int reg = 0; reg < 4; reg++) {
-      float v = best[fr][reg], v2 = best2[fr][reg];
-      int vi = bidx[fr][reg];
-#pragma unroll
-      for (int off = 8; off > 0; off >>= 1) {
-        const float ov = __shfl_xor(v, off, RAFT_AMD_WAVE);
-        const float ov2 = __shfl_xor(v2, off, RAFT_AMD_WAVE);
-        const int oi = __shfl_xor(vi, off, RAFT_AMD_WAVE);
-        float new2 = fminf(v2, ov2);
-        if (oi != vi) new2 = fminf(new2, fmaxf(v, ov));
-        v2 = new2;
-        if (ov < v || (ov == v && oi < vi)) { v = ov; vi = oi; }
-      }
-      best[fr][reg] = v;
-      best2[fr][reg] = v2;
-      bidx[fr][reg] = vi;
-    }
-  }
+  top2_reduce16(best, best2, bidx);
 
-  // combine the two column-half waves (wc = 0,1) of each row through LDS,
-  // then one wave per row-half writes. smem is free after the last barrier.
+  // combine the two column-half waves (wc = 0,1) of each row through LDS
+  // ([2][128]), then one wave per row-half writes
   __syncthreads();
-  float* comb_v = reinterpret_cast<float*>(smem);          // [2][128]
-  int* comb_i = reinterpret_cast<int*>(comb_v + 256);      // [2][128]
-  float* comb_v2 = reinterpret_cast<float*>(comb_i + 256); // [2][128]
   if ((lane & 15) == 0) {
 #pragma unroll
     for (int fr = 0; fr < 4; fr++)
 #pragma unroll
       for (int reg = 0; reg < 4; reg++) {
-        const int rl = wr * 64 + fr * 16 + (lane >> 4) * 4 + reg;  // 0..127
-        comb_v[wc * 128 + rl] = best[fr][reg];
-        comb_i[wc * 128 + rl] = bidx[fr][reg];
-        comb_v2[wc * 128 + rl] = best2[fr][reg];
+        const int rl = wr * 64 + fr * 16 + (lane >> 4) * 4 + reg;
+        top2_park<256>(smem, wc * 128 + rl, best[fr][reg], best2[fr][reg],
+                     bidx[fr][reg]);
       }
   }
   __syncthreads();
@@ -169,89 +119,50 @@ __global__ void fused_l2nn_kernel(const __bf16* __restrict__ x0,
 #pragma unroll
       for (int reg = 0; reg < 4; reg++) {
         const int rl = wr * 64 + fr * 16 + (lane >> 4) * 4 + reg;
-        float v0 = comb_v[rl], v1 = comb_v[128 + rl];
-        int i0 = comb_i[rl], i1 = comb_i[128 + rl];
-        const float s2 = fminf(fminf(comb_v2[rl], comb_v2[128 + rl]),
-                               fmaxf(v0, v1));
-        const bool take1 = (v1 < v0) || (v1 == v0 && i1 < i0);
-        const float v = take1 ? v1 : v0;
-        const int vi = take1 ? i1 : i0;
+        float v, v2;
+        int vi;
+        top2_merge_parked<2, 256, 1, 128, false>(smem, rl, v, v2, vi);
         const long long row = row0 + rl;
         if (row < m) {
           dmin[row] = fmaxf(v + xn[row], 0.f);
           amin[row] = vi;
-          if (dmin2) dmin2[row] = s2 + xn[row];  // second-best, unclamped
+          if (dmin2) dmin2[row] = v2 + xn[row];  // second-best, unclamped
         }
       }
   }
 }
 
-bool l2nn_phased() {
-  static const bool on = [] {
-    const char* e = getenv("RAFT_AMD_L2NN_PHASED");
-    return e && e[0] == '1';
-  }();
-  return on;
+template <int NSLICE, bool DB, bool PHASED>
+static void launch_v1(const SlicePtrs& p, const float* xn, const float* cn,
+                      float* dmin, int* amin, float* dmin2, long long m, int n,
+                      int d, hipStream_t stream) {
+  if constexpr (NSLICE == 3) {  // 96 KiB passes the default dynamic-LDS limit
+    static bool attr_set = false;
+    if (!attr_set) {
+      HIP_CHECK(hipFuncSetAttribute(
+          (const void*)&fused_l2nn_kernel<NSLICE, DB, PHASED>,
+          hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+      attr_set = true;
+    }
+  }
+  const size_t lds = (size_t)NSLICE * 2 * 8192 * sizeof(__bf16);
+  hipLaunchKernelGGL((fused_l2nn_kernel<NSLICE, DB, PHASED>),
+                     dim3((int)((m + 127) / 128)), dim3(256), lds, stream, p.x[0],
+                     p.x[1], p.x[2], p.c[0], p.c[1], p.c[2], xn, cn, dmin, amin,
+                     dmin2, m, n, d);
 }
 
-void launch_fused_l2nn_split(const void** xsl, const void** csl, const float* xn,
-                             const float* cn, float* dmin, int* amin, float* dmin2,
-                             long long m, int n, int d, int nslice,
-                             hipStream_t stream) {
-  const int grid = (int)((m + 127) / 128);
-  const size_t lds = (size_t)nslice * 2 * 8192 * sizeof(__bf16);
-  static const bool use_db = [] {
-    const char* e = getenv("RAFT_AMD_L2NN_DB");
-    return e && e[0] == '1';
-  }();
-  const __bf16* x0 = (const __bf16*)xsl[0];
-  const __bf16* x1 = (const __bf16*)(nslice > 1 ? xsl[1] : xsl[0]);
-  const __bf16* x2 = (const __bf16*)(nslice > 2 ? xsl[2] : xsl[0]);
-  const __bf16* c0 = (const __bf16*)csl[0];
-  const __bf16* c1 = (const __bf16*)(nslice > 1 ? csl[1] : csl[0]);
-  const __bf16* c2 = (const __bf16*)(nslice > 2 ? csl[2] : csl[0]);
-  switch (nslice) {
-    case 1:
-      if (use_db)
-        hipLaunchKernelGGL((fused_l2nn_kernel<1, true>), dim3(grid), dim3(256), lds,
-                           stream, x0, x1, x2, c0, c1, c2, xn, cn, dmin, amin, dmin2, m, n, d);
-      else
-        hipLaunchKernelGGL((fused_l2nn_kernel<1>), dim3(grid), dim3(256), lds, stream,
-                           x0, x1, x2, c0, c1, c2, xn, cn, dmin, amin, dmin2, m, n, d);
-      break;
-    case 2:
-      if (use_db)
-        hipLaunchKernelGGL((fused_l2nn_kernel<2, true>), dim3(grid), dim3(256), lds,
-                           stream, x0, x1, x2, c0, c1, c2, xn, cn, dmin, amin, dmin2, m, n, d);
-      else if (l2nn_phased())
-        hipLaunchKernelGGL((fused_l2nn_kernel<2, false, true>), dim3(grid), dim3(256),
-                           lds, stream, x0, x1, x2, c0, c1, c2, xn, cn, dmin, amin, dmin2, m, n, d);
-      else
-        hipLaunchKernelGGL((fused_l2nn_kernel<2>), dim3(grid), dim3(256), lds, stream,
-                           x0, x1, x2, c0, c1, c2, xn, cn, dmin, amin, dmin2, m, n, d);
-      break;
-    case 3: {
-      static bool attr_set = false;
-      if (!attr_set) {
-        HIP_CHECK(hipFuncSetAttribute((const void*)&fused_l2nn_kernel<3>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      96 * 1024));
-        HIP_CHECK(hipFuncSetAttribute((const void*)&fused_l2nn_kernel<3, true>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      96 * 1024));
-        attr_set = true;
-      }
-      if (use_db)
-        hipLaunchKernelGGL((fused_l2nn_kernel<3, true>), dim3(grid), dim3(256), lds,
-                           stream, x0, x1, x2, c0, c1, c2, xn, cn, dmin, amin, dmin2, m, n, d);
-      else
-        hipLaunchKernelGGL((fused_l2nn_kernel<3>), dim3(grid), dim3(256), lds, stream,
-                           x0, x1, x2, c0, c1, c2, xn, cn, dmin, amin, dmin2, m, n, d);
-      break;
-    }
-    default:
-      throw std::runtime_error("fused_l2nn: nslice must be 1, 2 or 3");
-  }
+void launch_l2nn_v1(const SlicePtrs& p, const float* xn, const float* cn,
+                    float* dmin, int* amin, float* dmin2, long long m, int n, int d,
+                    int nslice, L2nnEngine variant, hipStream_t stream) {
+#define L2NN_V1(NS, DB, PH) \
+  launch_v1<NS, DB, PH>(p, xn, cn, dmin, amin, dmin2, m, n, d, stream)
+  const bool db = variant == L2nnEngine::V1Db;
+  if (variant == L2nnEngine::V1Phased) L2NN_V1(2, false, true);  // resolver: nslice == 2
+  else if (nslice == 1) { if (db) L2NN_V1(1, true, false); else L2NN_V1(1, false, false); }
+  else if (nslice == 2) { if (db) L2NN_V1(2, true, false); else L2NN_V1(2, false, false); }
+  else { if (db) L2NN_V1(3, true, false); else L2NN_V1(3, false, false); }
+#undef L2NN_V1
 }
 
 }  // namespace raft_amd

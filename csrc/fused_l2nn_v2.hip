@@ -16,7 +16,8 @@
 
 #include <hip/hip_runtime.h>
 
-#include "mfma_common.h"
+#include "l2nn_engine.h"
+#include "l2nn_top2.h"
 
 namespace raft_amd {
 
@@ -201,10 +202,9 @@ __global__ void fused_l2nn_persist_kernel(
 }
 
 template <int NSLICE, int BM, int WR, int WC>
-static void launch_persist(const __bf16* x0, const __bf16* x1, const __bf16* x2,
-                           const __bf16* c0, const __bf16* c1, const __bf16* c2,
-                           const float* xn, const float* cn, float* dmin, int* amin,
-                           float* dmin2, long long m, int n, int d, hipStream_t stream) {
+static void launch_persist(const SlicePtrs& p, const float* xn, const float* cn,
+                           float* dmin, int* amin, float* dmin2, long long m, int n,
+                           int d, hipStream_t stream) {
   const int grid = (int)((m + BM - 1) / BM);
   const size_t lds =
       (size_t)NSLICE * (d / 64) * BM * 64 * 2 + (size_t)NSLICE * 8192 * 2;
@@ -216,8 +216,8 @@ static void launch_persist(const __bf16* x0, const __bf16* x1, const __bf16* x2,
     attr_set = true;
   }
   hipLaunchKernelGGL((fused_l2nn_persist_kernel<NSLICE, BM, WR, WC>), dim3(grid),
-                     dim3(WR * WC * 64), lds, stream, x0, x1, x2, c0, c1, c2, xn,
-                     cn, dmin, amin, dmin2, m, n, d);
+                     dim3(WR * WC * 64), lds, stream, p.x[0], p.x[1], p.x[2], p.c[0],
+                     p.c[1], p.c[2], xn, cn, dmin, amin, dmin2, m, n, d);
 }
 
 // ---------------------------------------------------------------------------
@@ -256,12 +256,7 @@ __global__ void fused_l2nn_w8_kernel(
 
   float best[4][4], best2[4][4];
   int bidx[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; a++)
-#pragma unroll
-    for (int b = 0; b < 4; b++) {
-      best[a][b] = INFINITY; best2[a][b] = INFINITY; bidx[a][b] = 0;
-    }
+  top2_init(best, best2, bidx);
 
   const int n_tiles = n / 256;
   const int k_tiles = d / 64;
@@ -317,64 +312,21 @@ __global__ void fused_l2nn_w8_kernel(
       __syncthreads();
     }
 
-    const int col_base = nt * 256 + wc * 64;
-#pragma unroll
-    for (int fr = 0; fr < 4; fr++) {
-#pragma unroll
-      for (int reg = 0; reg < 4; reg++) {
-#pragma unroll
-        for (int fc = 0; fc < 4; fc++) {
-          const int col = col_base + fc * 16 + (lane & 15);
-          const float s = cn[col] - 2.f * acc[fr][fc][reg];
-          // second-best via one v_med3_f32 (invariant best <= best2)
-          best2[fr][reg] = __builtin_amdgcn_fmed3f(s, best[fr][reg],
-                                                   best2[fr][reg]);
-          if (s < best[fr][reg]) {
-            best[fr][reg] = s;
-            bidx[fr][reg] = col;
-          }
-        }
-      }
-    }
+    top2_fold_tile(acc, cn, nt * 256 + wc * 64 + (lane & 15), best, best2, bidx);
   }
 
-  // ONE cross-lane top-2 reduce after the nt loop (lane column sets disjoint)
-#pragma unroll
-  for (int fr = 0; fr < 4; fr++) {
-#pragma unroll
-    for (int reg = 0; reg < 4; reg++) {
-      float v = best[fr][reg], v2 = best2[fr][reg];
-      int vi = bidx[fr][reg];
-#pragma unroll
-      for (int off = 8; off > 0; off >>= 1) {
-        const float ov = __shfl_xor(v, off, RAFT_AMD_WAVE);
-        const float ov2 = __shfl_xor(v2, off, RAFT_AMD_WAVE);
-        const int oi = __shfl_xor(vi, off, RAFT_AMD_WAVE);
-        float new2 = fminf(v2, ov2);
-        if (oi != vi) new2 = fminf(new2, fmaxf(v, ov));
-        v2 = new2;
-        if (ov < v || (ov == v && oi < vi)) { v = ov; vi = oi; }
-      }
-      best[fr][reg] = v;
-      best2[fr][reg] = v2;
-      bidx[fr][reg] = vi;
-    }
-  }
-
-  // combine the 4 column-slice waves per row through LDS, then write
+  // ONE cross-lane reduce after the nt loop, then the 4 column-slice waves
+  // of each row combine through LDS ([4][128]) and one wave per row-half writes
+  top2_reduce16(best, best2, bidx);
   __syncthreads();
-  float* comb_v = reinterpret_cast<float*>(smem);          // [4][128]
-  int* comb_i = reinterpret_cast<int*>(comb_v + 512);      // [4][128]
-  float* comb_v2 = reinterpret_cast<float*>(comb_i + 512); // [4][128]
   if ((lane & 15) == 0) {
 #pragma unroll
     for (int fr = 0; fr < 4; fr++)
 #pragma unroll
       for (int reg = 0; reg < 4; reg++) {
-        const int rl = wr * 64 + fr * 16 + (lane >> 4) * 4 + reg;  // 0..127
-        comb_v[wc * 128 + rl] = best[fr][reg];
-        comb_i[wc * 128 + rl] = bidx[fr][reg];
-        comb_v2[wc * 128 + rl] = best2[fr][reg];
+        const int rl = wr * 64 + fr * 16 + (lane >> 4) * 4 + reg;
+        top2_park<512>(smem, wc * 128 + rl, best[fr][reg], best2[fr][reg],
+                     bidx[fr][reg]);
       }
   }
   __syncthreads();
@@ -384,31 +336,23 @@ __global__ void fused_l2nn_w8_kernel(
 #pragma unroll
       for (int reg = 0; reg < 4; reg++) {
         const int rl = wr * 64 + fr * 16 + (lane >> 4) * 4 + reg;
-        float v = comb_v[rl];
-        int vi = comb_i[rl];
-        float s2 = comb_v2[rl];
-        for (int q = 1; q < 4; q++) {
-          const float ov = comb_v[q * 128 + rl];
-          const int oi = comb_i[q * 128 + rl];
-          const float ov2 = comb_v2[q * 128 + rl];
-          s2 = fminf(fminf(s2, ov2), fmaxf(v, ov));
-          if (ov < v || (ov == v && oi < vi)) { v = ov; vi = oi; }
-        }
+        float v, v2;
+        int vi;
+        top2_merge_parked<4, 512, 1, 128, false>(smem, rl, v, v2, vi);
         const long long row = row0 + rl;
         if (row < m) {
           dmin[row] = fmaxf(v + xn[row], 0.f);
           amin[row] = vi;
-          if (dmin2) dmin2[row] = s2 + xn[row];
+          if (dmin2) dmin2[row] = v2 + xn[row];
         }
       }
   }
 }
 
 template <int NSLICE>
-static void launch_w8(const __bf16* x0, const __bf16* x1, const __bf16* x2,
-                      const __bf16* c0, const __bf16* c1, const __bf16* c2,
-                      const float* xn, const float* cn, float* dmin, int* amin,
-                      float* dmin2, long long m, int n, int d, hipStream_t stream) {
+static void launch_w8(const SlicePtrs& p, const float* xn, const float* cn,
+                      float* dmin, int* amin, float* dmin2, long long m, int n,
+                      int d, hipStream_t stream) {
   const int grid = (int)((m + 127) / 128);
   const size_t lds = (size_t)NSLICE * (8192 + 16384) * sizeof(__bf16);
   static bool attr_set = false;
@@ -419,66 +363,30 @@ static void launch_w8(const __bf16* x0, const __bf16* x1, const __bf16* x2,
     attr_set = true;
   }
   hipLaunchKernelGGL((fused_l2nn_w8_kernel<NSLICE>), dim3(grid), dim3(512), lds,
-                     stream, x0, x1, x2, c0, c1, c2, xn, cn, dmin, amin, dmin2,
-                     m, n, d);
+                     stream, p.x[0], p.x[1], p.x[2], p.c[0], p.c[1], p.c[2], xn, cn,
+                     dmin, amin, dmin2, m, n, d);
 }
 
-bool fused_l2nn_w8_supported(int nslice, int n, int d) {
-  // measured (10M x 256 k=1024): w8 wins only for NSLICE=3 (staging-bound:
-  // halved X re-reads beat the lost cross-block barrier overlap); the 4-wave
-  // 2-block v1 kernel wins for NSLICE<=2 (34.3 vs 38.0 ms/step).
-  // RAFT_AMD_L2NN_W8=2 forces w8 for ALL nslice (A/B experiments).
-  static const bool force_all = [] {
-    const char* e = getenv("RAFT_AMD_L2NN_W8");
-    return e && e[0] == '2';
-  }();
-  if (n % 256 != 0 || d % 64 != 0) return false;
-  return force_all || nslice == 3;
+void launch_l2nn_w8(const SlicePtrs& p, const float* xn, const float* cn, float* dmin,
+                    int* amin, float* dmin2, long long m, int n, int d, int nslice,
+                    hipStream_t stream) {
+  if (nslice == 1) launch_w8<1>(p, xn, cn, dmin, amin, dmin2, m, n, d, stream);
+  else if (nslice == 2) launch_w8<2>(p, xn, cn, dmin, amin, dmin2, m, n, d, stream);
+  else launch_w8<3>(p, xn, cn, dmin, amin, dmin2, m, n, d, stream);
 }
 
-void launch_fused_l2nn_w8(const void** xsl, const void** csl, const float* xn,
-                          const float* cn, float* dmin, int* amin, float* dmin2,
-                          long long m, int n, int d, int nslice, hipStream_t stream) {
-  const __bf16* x0 = (const __bf16*)xsl[0];
-  const __bf16* x1 = (const __bf16*)(nslice > 1 ? xsl[1] : xsl[0]);
-  const __bf16* x2 = (const __bf16*)(nslice > 2 ? xsl[2] : xsl[0]);
-  const __bf16* c0 = (const __bf16*)csl[0];
-  const __bf16* c1 = (const __bf16*)(nslice > 1 ? csl[1] : csl[0]);
-  const __bf16* c2 = (const __bf16*)(nslice > 2 ? csl[2] : csl[0]);
+void launch_l2nn_persist(const SlicePtrs& p, const float* xn, const float* cn,
+                         float* dmin, int* amin, float* dmin2, long long m, int n,
+                         int d, int nslice, hipStream_t stream) {
+  // NSLICE=3 keeps X within LDS with BM=64 for d in (128, 256]
   if (nslice == 1)
-    launch_w8<1>(x0, x1, x2, c0, c1, c2, xn, cn, dmin, amin, dmin2, m, n, d, stream);
+    launch_persist<1, 128, 2, 4>(p, xn, cn, dmin, amin, dmin2, m, n, d, stream);
   else if (nslice == 2)
-    launch_w8<2>(x0, x1, x2, c0, c1, c2, xn, cn, dmin, amin, dmin2, m, n, d, stream);
+    launch_persist<2, 128, 2, 4>(p, xn, cn, dmin, amin, dmin2, m, n, d, stream);
+  else if (d <= 128)
+    launch_persist<3, 128, 2, 4>(p, xn, cn, dmin, amin, dmin2, m, n, d, stream);
   else
-    launch_w8<3>(x0, x1, x2, c0, c1, c2, xn, cn, dmin, amin, dmin2, m, n, d, stream);
-}
-
-// returns true when a persistent variant covers (nslice, d)
-bool fused_l2nn_persist_supported(int nslice, int d) {
-  if (d % 64 != 0) return false;
-  if (nslice <= 2) return d <= 256;
-  return d <= 256;  // NSLICE=3 uses BM=64 for d in (128, 256]
-}
-
-void launch_fused_l2nn_persist(const void** xsl, const void** csl, const float* xn,
-                               const float* cn, float* dmin, int* amin, float* dmin2,
-                               long long m, int n, int d, int nslice,
-                               hipStream_t stream) {
-  const __bf16* x0 = (const __bf16*)xsl[0];
-  const __bf16* x1 = (const __bf16*)(nslice > 1 ? xsl[1] : xsl[0]);
-  const __bf16* x2 = (const __bf16*)(nslice > 2 ? xsl[2] : xsl[0]);
-  const __bf16* c0 = (const __bf16*)csl[0];
-  const __bf16* c1 = (const __bf16*)(nslice > 1 ? csl[1] : csl[0]);
-  const __bf16* c2 = (const __bf16*)(nslice > 2 ? csl[2] : csl[0]);
-  if (nslice == 1) {
-    launch_persist<1, 128, 2, 4>(x0, x1, x2, c0, c1, c2, xn, cn, dmin, amin, dmin2, m, n, d, stream);
-  } else if (nslice == 2) {
-    launch_persist<2, 128, 2, 4>(x0, x1, x2, c0, c1, c2, xn, cn, dmin, amin, dmin2, m, n, d, stream);
-  } else if (d <= 128) {
-    launch_persist<3, 128, 2, 4>(x0, x1, x2, c0, c1, c2, xn, cn, dmin, amin, dmin2, m, n, d, stream);
-  } else {
-    launch_persist<3, 64, 1, 8>(x0, x1, x2, c0, c1, c2, xn, cn, dmin, amin, dmin2, m, n, d, stream);
-  }
+    launch_persist<3, 64, 1, 8>(p, xn, cn, dmin, amin, dmin2, m, n, d, stream);
 }
 
 }  // namespace raft_amd

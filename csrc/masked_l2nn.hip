@@ -19,8 +19,8 @@
 // Grid: 1D, block = (row tile, column split). A block walks the column tiles
 // of its split with the running (best, second-best, index) triple in
 // registers, as fused_l2nn_kernel does, and writes one partial triple per row;
-// masked_l2nn_combine_kernel merges the splits (disjoint column ranges -> a
-// plain top-2 merge), adds ||x||^2 and turns "no candidate" into (+inf, -1).
+// l2nn_combine_kernel<true> (l2nn_top2.h) merges the splits, adds ||x||^2 and
+// turns "no candidate" into (+inf, -1).
 //
 // Tile skip: before the K-loop the block decides whether any (row, column)
 // pair of the tile is allowed. With adj, each row builds the tile's 128-bit
@@ -35,12 +35,10 @@
 
 #include <hip/hip_runtime.h>
 
-#include "mfma_common.h"
+#include "l2nn_engine.h"
+#include "l2nn_top2.h"
 
 namespace raft_amd {
-
-// index of "no allowed column seen": loses every smaller-index tie-break
-constexpr int MASKED_NN_NONE = 0x7fffffff;
 
 template <int NSLICE, bool HAS_ADJ>
 __launch_bounds__(256, 2)
@@ -92,14 +90,7 @@ __global__ void masked_l2nn_kernel(const __bf16* __restrict__ x0,
 
   float best[4][4], best2[4][4];
   int bidx[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; a++)
-#pragma unroll
-    for (int b = 0; b < 4; b++) {
-      best[a][b] = INFINITY;
-      best2[a][b] = INFINITY;
-      bidx[a][b] = MASKED_NN_NONE;
-    }
+  top2_init(best, best2, bidx, MASKED_NN_NONE);
   unsigned int n_visited = 0, n_skipped = 0;
 
   for (int ct = ct0; ct < ct1; ct++) {
@@ -184,112 +175,26 @@ __global__ void masked_l2nn_kernel(const __bf16* __restrict__ x0,
           const bool ok = HAS_ADJ ? ((mk >> (fc * 16)) & 1ull) != 0ull
                                   : yg_r[fc] != xgv;
           const float s = ok ? yn_r[fc] - 2.f * acc[fr][fc][reg] : INFINITY;
-          best2[fr][reg] = __builtin_amdgcn_fmed3f(s, best[fr][reg],
-                                                   best2[fr][reg]);
-          if (s < best[fr][reg]) {
-            best[fr][reg] = s;
-            bidx[fr][reg] = colb + fc * 16;
-          }
+          top2_push(best[fr][reg], best2[fr][reg], bidx[fr][reg], s, colb + fc * 16);
         }
       }
     }
   }
 
-  // ONE cross-lane top-2 reduce per (fr, reg) over the 16 lanes of a row group
-#pragma unroll
-  for (int fr = 0; fr < 4; fr++) {
-#pragma unroll
-    for (int reg = 0; reg < 4; reg++) {
-      float v = best[fr][reg], v2 = best2[fr][reg];
-      int vi = bidx[fr][reg];
-#pragma unroll
-      for (int off = 8; off > 0; off >>= 1) {
-        const float ov = __shfl_xor(v, off, RAFT_AMD_WAVE);
-        const float ov2 = __shfl_xor(v2, off, RAFT_AMD_WAVE);
-        const int oi = __shfl_xor(vi, off, RAFT_AMD_WAVE);
-        float new2 = fminf(v2, ov2);
-        if (oi != vi) new2 = fminf(new2, fmaxf(v, ov));
-        v2 = new2;
-        if (ov < v || (ov == v && oi < vi)) { v = ov; vi = oi; }
-      }
-      best[fr][reg] = v;
-      best2[fr][reg] = v2;
-      bidx[fr][reg] = vi;
-    }
-  }
-
-  // combine the two column-half waves of each row through the (dead) staging
-  // LDS, then one thread per row writes the split's partial
-  __syncthreads();
-  float* comb_v = reinterpret_cast<float*>(smem);           // [2][128]
-  int* comb_i = reinterpret_cast<int*>(comb_v + 256);       // [2][128]
-  float* comb_v2 = reinterpret_cast<float*>(comb_i + 256);  // [2][128]
-  if ((lane & 15) == 0) {
-#pragma unroll
-    for (int fr = 0; fr < 4; fr++)
-#pragma unroll
-      for (int reg = 0; reg < 4; reg++) {
-        const int rl = wr * 64 + fr * 16 + (lane >> 4) * 4 + reg;
-        comb_v[wc * 128 + rl] = best[fr][reg];
-        comb_i[wc * 128 + rl] = bidx[fr][reg];
-        comb_v2[wc * 128 + rl] = best2[fr][reg];
-      }
-  }
-  __syncthreads();
-  if (t < 128) {
-    const long long row = row0 + t;
-    if (row < m) {
-      const float v0 = comb_v[t], v1 = comb_v[128 + t];
-      const int i0 = comb_i[t], i1 = comb_i[128 + t];
-      float s2 = fminf(comb_v2[t], comb_v2[128 + t]);
-      if (i0 != i1) s2 = fminf(s2, fmaxf(v0, v1));
-      const bool take1 = (v1 < v0) || (v1 == v0 && i1 < i0);
-      const long long o = (long long)sp * m + row;
-      pd[o] = take1 ? v1 : v0;
-      pi[o] = take1 ? i1 : i0;
-      pd2[o] = s2;
-    }
-  }
+  // ONE cross-lane reduce, then the two column-half waves of each row combine
+  // through the (dead) staging LDS ([2][128]) and one thread per row writes
+  // the split's partial. Index-guarded: both halves may hold MASKED_NN_NONE.
+  top2_reduce16(best, best2, bidx);
+  top2_park_tile<4, 256, 1, 128>(smem, (lane & 15) == 0, wr * 64, lane, wc, best,
+                                 best2, bidx);
+  if (t < 128 && row0 + t < m)
+    top2_write_partial<2, 256, 1, 128, true>(smem, t, pd, pd2, pi,
+                                             (long long)sp * m + row0 + t);
   // one vector atomic per counter per block
   if (t == 0) {
     if (n_visited) atomicAdd(&counters[0], (unsigned long long)n_visited);
     if (n_skipped) atomicAdd(&counters[1], (unsigned long long)n_skipped);
   }
-}
-
-// Merge the n_split partial triples of every row. Splits cover disjoint column
-// ranges, so the second-best is the plain top-2 merge; equal scores go to the
-// smaller column index. Rows with no allowed column get (+inf, -1).
-__global__ void masked_l2nn_combine_kernel(const float* __restrict__ pd,
-                                           const float* __restrict__ pd2,
-                                           const int* __restrict__ pi,
-                                           const float* __restrict__ xn,
-                                           float* __restrict__ dmin,
-                                           int* __restrict__ amin,
-                                           float* __restrict__ dmin2,
-                                           long long m, int n_split) {
-  const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (row >= m) return;
-  float v = INFINITY, v2 = INFINITY;
-  int vi = MASKED_NN_NONE;
-  for (int g = 0; g < n_split; g++) {
-    const long long o = (long long)g * m + row;
-    const float b = pd[o], b2 = pd2[o];
-    const int bi = pi[o];
-    v2 = fminf(v2, b2);
-    if (bi != vi) v2 = fminf(v2, fmaxf(v, b));
-    if (b < v || (b == v && bi < vi)) { v = b; vi = bi; }
-  }
-  if (vi == MASKED_NN_NONE) {
-    dmin[row] = INFINITY;
-    amin[row] = -1;
-    dmin2[row] = INFINITY;
-    return;
-  }
-  const float x = xn[row];
-  dmin[row] = fmaxf(v + x, 0.f);
-  amin[row] = vi;
-  dmin2[row] = v2 + x;  // second-best, unclamped (+inf: single candidate)
 }
 
 void launch_masked_l2nn(const void** xsl, const void** csl, const float* xn,
@@ -312,12 +217,9 @@ void launch_masked_l2nn(const void** xsl, const void** csl, const float* xn,
   if (blocks > 2147483647ll)
     throw std::runtime_error("masked_l2nn: grid too large, chunk the rows");
   const bool has_adj = adj != nullptr;
+  const SlicePtrs p(xsl, csl, nslice);
   const size_t lds = (size_t)nslice * 2 * 8192 * sizeof(__bf16) +
                      (128 + 128 + 512) * sizeof(int);
-  const __bf16* x0 = (const __bf16*)xsl[0];
-  const __bf16* x1 = (const __bf16*)(nslice > 1 ? xsl[1] : xsl[0]);
-  const __bf16* c0 = (const __bf16*)csl[0];
-  const __bf16* c1 = (const __bf16*)(nslice > 1 ? csl[1] : csl[0]);
   const dim3 grid((unsigned)blocks);
   if (nslice == 2) {
     // two slices + the mask state pass the 64 KiB default dynamic-LDS limit
@@ -334,17 +236,16 @@ void launch_masked_l2nn(const void** xsl, const void** csl, const float* xn,
   }
 #define RAFT_MASKED_NN_LAUNCH(NS, ADJ)                                          \
   hipLaunchKernelGGL((masked_l2nn_kernel<NS, ADJ>), grid, dim3(256), lds,       \
-                     stream, x0, x1, c0, c1, yn, y_group, adj, x_group, pd,     \
-                     pd2, pi, counters, m, n, d, adj_words, n_split, tps)
+                     stream, p.x[0], p.x[1], p.c[0], p.c[1], yn, y_group, adj,  \
+                     x_group, pd, pd2, pi, counters, m, n, d, adj_words, n_split, \
+                     tps)
   if (nslice == 1 && has_adj) RAFT_MASKED_NN_LAUNCH(1, true);
   else if (nslice == 1) RAFT_MASKED_NN_LAUNCH(1, false);
   else if (nslice == 2 && has_adj) RAFT_MASKED_NN_LAUNCH(2, true);
   else if (nslice == 2) RAFT_MASKED_NN_LAUNCH(2, false);
   else throw std::runtime_error("masked_l2nn: nslice must be 1 or 2");
 #undef RAFT_MASKED_NN_LAUNCH
-  hipLaunchKernelGGL(masked_l2nn_combine_kernel, dim3((unsigned)((m + 255) / 256)),
-                     dim3(256), 0, stream, pd, pd2, pi, xn, dmin, amin, dmin2, m,
-                     n_split);
+  launch_l2nn_combine<true>(pd, pd2, pi, xn, dmin, amin, dmin2, m, n_split, stream);
 }
 
 // ---------------------------------------------------------------------------

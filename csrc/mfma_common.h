@@ -44,6 +44,17 @@ __device__ __forceinline__ void mfma_stage_tile128(const __bf16* __restrict__ g,
   }
 }
 
+// Bijective XCD-contiguous block remap (guide T1): default dispatch
+// round-robins blockIdx over the 8 XCDs, so XCD x = bid%8 runs slots bid/8.
+// Returns the tile index that gives each XCD a contiguous band of the nwg
+// tiles (the first nwg%8 XCDs take one more), so an XCD's resident blocks
+// share panels through its own L2.
+__device__ __forceinline__ int xcd_contiguous_tile(int bid, int nwg) {
+  const int q = nwg >> 3, r = nwg & 7;
+  const int xcd = bid & 7, slot = bid >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+}
+
 // XCD-contiguous 8x8 super-tiled (row-tile, col-tile) decode for 2D tile
 // grids (guide T1 + super-tiling): the bijective remap gives each XCD a
 // contiguous slot range, and consecutive 64-slot windows decode to an
@@ -59,11 +70,7 @@ __device__ __forceinline__ void xcd_supertile_decode(int rg, long long* rt,
                                                      long long* ct) {
   const bool cm = rg < 0;
   if (cm) rg = -rg;
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int q = nwg >> 3, r = nwg & 7;
-  const int xcd = bid & 7, slot = bid >> 3;
-  const int t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+  const int t = xcd_contiguous_tile(blockIdx.x, gridDim.x);
   const int g = t >> 6, w = t & 63;
   const int wr = cm ? (w >> 3) : (w & 7);
   const int wc = cm ? (w & 7) : (w >> 3);

@@ -241,11 +241,7 @@ __global__ void pairwise_l2_filter_px_kernel(
 
   // bijective XCD-contiguous remap, COLUMN-group-major (blocks sharing a C
   // group land on one XCD)
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int q = nwg >> 3, r = nwg & 7;
-  const int xcd = bid & 7, slot = bid >> 3;
-  const int t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+  const int t = xcd_contiguous_tile(blockIdx.x, gridDim.x);
   const long long row0 = (long long)(t % n_row_tiles) * 128;
   const int ctg = t / n_row_tiles;
   const long long col_base = (long long)ctg * CT * 128;
