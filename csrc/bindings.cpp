@@ -13,6 +13,7 @@
 #include <limits>
 
 #include "l2nn_engine.h"
+#include "pairwise_variant.h"
 
 namespace raft_amd {
 
@@ -97,19 +98,6 @@ template <typename T>
 void launch_select_k_generic_t(const T*, const long long*, long long, long long,
                                T*, long long*, long long, long long, bool,
                                hipStream_t);
-// from pairwise_mfma.hip
-void launch_pairwise_l2_mfma(const void**, const void**, const float*, const float*,
-                             float*, long long, long long, int, long long, int, bool,
-                             hipStream_t);
-void launch_pairwise_l2_mfma256(const void**, const void**, const float*, const float*,
-                                float*, long long, long long, int, long long, int, bool,
-                                hipStream_t);
-void launch_pairwise_l2_filter(const void**, const void**, const float*, const float*,
-                               const float*, float*, int*, int*, int, long long,
-                               long long, long long, int, int, hipStream_t);
-void launch_pairwise_l2_filter256(const void**, const void**, const float*, const float*,
-                                  const float*, float*, int*, int*, int, long long,
-                                  long long, long long, int, int, hipStream_t);
 void launch_eps_neighbors_l2sq(const void**, const void**, const float*, const float*,
                                const float*, const float*, unsigned int*,
                                unsigned long long*, float, float, float, long long,
@@ -549,51 +537,63 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> fused_l2nn_split(
   return {dmin, amin, dmin2};
 }
 
-torch::Tensor pairwise_l2_mfma(std::vector<torch::Tensor> x_slices,
-                               std::vector<torch::Tensor> y_slices,
-                               torch::Tensor xn, torch::Tensor yn,
-                               c10::optional<torch::Tensor> out, bool sqrt_out) {
-  const int nslice = (int)x_slices.size();
-  TORCH_CHECK(nslice >= 1 && nslice <= 3 && y_slices.size() == x_slices.size());
+// one pairwise L2 call: checked bf16 slices, shape, and the kernel `variant`
+// resolves to ("auto" -> environment and defaults; an unknown name or a named
+// variant that cannot run the shape is an error, never a fallback)
+struct PwCall {
   const void* xsl[3];
   const void* csl[3];
-  for (int s = 0; s < nslice; s++) {
+  int nslice;
+  long long m, n, d;
+  raft_amd::PwPlan plan;
+};
+
+static PwCall pw_call(raft_amd::PwFamily family, const char* who,
+                      const std::vector<torch::Tensor>& x_slices,
+                      const std::vector<torch::Tensor>& y_slices,
+                      const std::string& variant) {
+  PwCall c;
+  c.nslice = (int)x_slices.size();
+  TORCH_CHECK(c.nslice >= 1 && c.nslice <= 3 && y_slices.size() == x_slices.size());
+  for (int s = 0; s < c.nslice; s++) {
     TORCH_CHECK(x_slices[s].is_cuda() && x_slices[s].scalar_type() == torch::kBFloat16
                 && x_slices[s].is_contiguous());
     TORCH_CHECK(y_slices[s].is_cuda() && y_slices[s].scalar_type() == torch::kBFloat16
                 && y_slices[s].is_contiguous());
-    xsl[s] = x_slices[s].data_ptr();
-    csl[s] = y_slices[s].data_ptr();
+    c.xsl[s] = x_slices[s].data_ptr();
+    c.csl[s] = y_slices[s].data_ptr();
   }
-  const long long m = x_slices[0].size(0);
-  const long long n = y_slices[0].size(0);
-  const long long d = x_slices[0].size(1);
-  TORCH_CHECK(d % 64 == 0, "pairwise_l2_mfma: d must be a multiple of 64");
+  c.m = x_slices[0].size(0);
+  c.n = y_slices[0].size(0);
+  c.d = x_slices[0].size(1);
+  TORCH_CHECK(c.d % 64 == 0, who, ": d must be a multiple of 64");
+  bool known;
+  const auto v = raft_amd::pw_variant_from_name(family, variant, &known);
+  TORCH_CHECK(known, who, ": unknown variant '", variant, "'");
+  c.plan = raft_amd::pw_resolve_variant(family, c.nslice, c.m, c.n, (int)c.d, v);
+  TORCH_CHECK(c.plan.error.empty(), c.plan.error, " (nslice=", c.nslice, ", m=", c.m,
+              ", n=", c.n, ", d=", c.d, ")");
+  return c;
+}
+
+torch::Tensor pairwise_l2_mfma(std::vector<torch::Tensor> x_slices,
+                               std::vector<torch::Tensor> y_slices,
+                               torch::Tensor xn, torch::Tensor yn,
+                               c10::optional<torch::Tensor> out, bool sqrt_out,
+                               const std::string& variant) {
+  PwCall c = pw_call(raft_amd::PwFamily::Tile, "pairwise_l2_mfma", x_slices,
+                           y_slices, variant);
   torch::Tensor o;
   if (out.has_value()) {
     o = out.value();
-    TORCH_CHECK(o.is_contiguous() && o.size(0) >= m && o.size(1) == n);
+    TORCH_CHECK(o.is_contiguous() && o.size(0) >= c.m && o.size(1) == c.n);
   } else {
-    o = torch::empty({m, n}, xn.options());
+    o = torch::empty({c.m, c.n}, xn.options());
   }
-  static const bool use_256 = [] {
-    const char* e = getenv("RAFT_AMD_PW256");
-    return e && e[0] == '1';
-  }();
-  if (use_256 && nslice <= 2 && m >= 512 && n >= 512) {
-    // 256x256-tile kernel (BK=32 counted-vmcnt): 4x fewer workgroups, but
-    // 1 block/CU serializes the tile-store phase with the K-loop — measured
-    // 547 vs the 128^2 kernel's 736 Gdist/s at 1Mx128 (round 2); kept for
-    // A/B via RAFT_AMD_PW256=1
-    raft_amd::launch_pairwise_l2_mfma256(xsl, csl, xn.data_ptr<float>(),
-                                         yn.data_ptr<float>(), o.data_ptr<float>(),
-                                         m, n, (int)d, o.size(1), nslice, sqrt_out,
-                                         cur_stream());
-  } else {
-    raft_amd::launch_pairwise_l2_mfma(xsl, csl, xn.data_ptr<float>(), yn.data_ptr<float>(),
-                                      o.data_ptr<float>(), m, n, (int)d, o.size(1),
-                                      nslice, sqrt_out, cur_stream());
-  }
+  raft_amd::launch_pairwise_l2_tile(c.plan, c.xsl, c.csl, xn.data_ptr<float>(),
+                                    yn.data_ptr<float>(), o.data_ptr<float>(), c.m, c.n,
+                                    (int)c.d, o.size(1), c.nslice, sqrt_out,
+                                    cur_stream());
   return o;
 }
 
@@ -614,44 +614,18 @@ void l2nn_verify_repair(torch::Tensor x, torch::Tensor c, torch::Tensor xn,
 void pairwise_l2_filter(std::vector<torch::Tensor> x_slices,
                         std::vector<torch::Tensor> y_slices, torch::Tensor xn,
                         torch::Tensor yn, torch::Tensor thr, torch::Tensor out_d,
-                        torch::Tensor out_i, torch::Tensor cnt, int64_t col_offset) {
-  const int nslice = (int)x_slices.size();
-  TORCH_CHECK(nslice >= 1 && nslice <= 3 && y_slices.size() == x_slices.size());
-  const void* xsl[3];
-  const void* csl[3];
-  for (int s = 0; s < nslice; s++) {
-    TORCH_CHECK(x_slices[s].is_cuda() && x_slices[s].scalar_type() == torch::kBFloat16
-                && x_slices[s].is_contiguous());
-    TORCH_CHECK(y_slices[s].is_cuda() && y_slices[s].scalar_type() == torch::kBFloat16
-                && y_slices[s].is_contiguous());
-    xsl[s] = x_slices[s].data_ptr();
-    csl[s] = y_slices[s].data_ptr();
-  }
-  const long long m = x_slices[0].size(0);
-  const long long n = y_slices[0].size(0);
-  const long long d = x_slices[0].size(1);
-  TORCH_CHECK(d % 64 == 0, "pairwise_l2_filter: d must be a multiple of 64");
+                        torch::Tensor out_i, torch::Tensor cnt, int64_t col_offset,
+                        const std::string& variant) {
+  PwCall c = pw_call(raft_amd::PwFamily::Filter, "pairwise_l2_filter", x_slices,
+                           y_slices, variant);
   const int cap = (int)out_d.size(1);
-  TORCH_CHECK(out_d.size(0) == m && out_i.sizes() == out_d.sizes());
-  TORCH_CHECK(cnt.scalar_type() == torch::kInt32 && cnt.numel() == m);
-  static const bool use_f256 = [] {
-    const char* e = getenv("RAFT_AMD_FILTER256");
-    return e && e[0] == '1';
-  }();  // A/B @100M-row kNN: 128-tile 9006 q/s vs 256-tile 7226 — the 4-wave
-        // 2-block filter wins (same pattern as the fused L2-NN A/B)
-  if (use_f256 && nslice <= 2 && m >= 512 && n >= 512) {
-    raft_amd::launch_pairwise_l2_filter256(xsl, csl, xn.data_ptr<float>(),
-                                           yn.data_ptr<float>(), thr.data_ptr<float>(),
-                                           out_d.data_ptr<float>(), out_i.data_ptr<int>(),
-                                           cnt.data_ptr<int>(), cap, col_offset, m, n,
-                                           (int)d, nslice, cur_stream());
-  } else {
-    raft_amd::launch_pairwise_l2_filter(xsl, csl, xn.data_ptr<float>(),
-                                        yn.data_ptr<float>(), thr.data_ptr<float>(),
-                                        out_d.data_ptr<float>(), out_i.data_ptr<int>(),
-                                        cnt.data_ptr<int>(), cap, col_offset, m, n,
-                                        (int)d, nslice, cur_stream());
-  }
+  TORCH_CHECK(out_d.size(0) == c.m && out_i.sizes() == out_d.sizes());
+  TORCH_CHECK(cnt.scalar_type() == torch::kInt32 && cnt.numel() == c.m);
+  raft_amd::launch_pairwise_l2_filter(c.plan, c.xsl, c.csl, xn.data_ptr<float>(),
+                                      yn.data_ptr<float>(), thr.data_ptr<float>(),
+                                      out_d.data_ptr<float>(), out_i.data_ptr<int>(),
+                                      cnt.data_ptr<int>(), cap, col_offset, c.m, c.n,
+                                      (int)c.d, c.nslice, cur_stream());
 }
 
 const unsigned int* bitmap_words(const torch::Tensor& bm, const char* who) {
@@ -1244,7 +1218,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("x"), pybind11::arg("row_off") = pybind11::none(),
         pybind11::arg("k"), pybind11::arg("select_min") = true);
   m.def("pairwise_l2_filter", &pairwise_l2_filter,
-        "threshold-filtered pairwise L2 candidate emission (fused kNN)");
+        "threshold-filtered pairwise L2 candidate emission (fused kNN); variant "
+        "names one kernel (csrc/pairwise_variant.h) and raises if it cannot run "
+        "the shape",
+        pybind11::arg("x_slices"), pybind11::arg("y_slices"), pybind11::arg("xn"),
+        pybind11::arg("yn"), pybind11::arg("thr"), pybind11::arg("out_d"),
+        pybind11::arg("out_i"), pybind11::arg("cnt"), pybind11::arg("col_offset"),
+        pybind11::arg("variant") = "auto");
   m.def("eps_neighbors_l2sq", &eps_neighbors_l2sq,
         "verified eps-neighborhood (squared L2) packed adjacency bitmap",
         pybind11::arg("x_slices"), pybind11::arg("y_slices"), pybind11::arg("xn"),
@@ -1272,10 +1252,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bitmap_rows_expand", &bitmap_rows_expand,
         "row-padded bitmap -> dense bool [m, n]");
   m.def("pairwise_l2_mfma", &pairwise_l2_mfma,
-        "fused split-bf16 MFMA pairwise L2 tile (single-write epilogue)",
+        "fused split-bf16 MFMA pairwise L2 tile (single-write epilogue); variant "
+        "names one kernel (csrc/pairwise_variant.h) and raises if it cannot run "
+        "the shape",
         pybind11::arg("x_slices"), pybind11::arg("y_slices"), pybind11::arg("xn"),
         pybind11::arg("yn"), pybind11::arg("out") = pybind11::none(),
-        pybind11::arg("sqrt_out") = false);
+        pybind11::arg("sqrt_out") = false, pybind11::arg("variant") = "auto");
   m.def("l2nn_verify_repair", &l2nn_verify_repair,
         pybind11::arg("x"), pybind11::arg("c"), pybind11::arg("xn"),
         pybind11::arg("dmin"), pybind11::arg("amin"), pybind11::arg("dmin2"),

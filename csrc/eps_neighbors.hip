@@ -29,12 +29,7 @@ namespace raft_amd {
 
 template <int NSLICE, bool VERIFY>
 __launch_bounds__(256, 2)
-__global__ void eps_neighbors_l2sq_kernel(const __bf16* __restrict__ x0,
-                                          const __bf16* __restrict__ x1,
-                                          const __bf16* __restrict__ x2,
-                                          const __bf16* __restrict__ c0,
-                                          const __bf16* __restrict__ c1,
-                                          const __bf16* __restrict__ c2,
+__global__ void eps_neighbors_l2sq_kernel(const SlicePtrs p,
                                           const float* __restrict__ xn,
                                           const float* __restrict__ yn,
                                           const float* __restrict__ xf,
@@ -45,33 +40,12 @@ __global__ void eps_neighbors_l2sq_kernel(const __bf16* __restrict__ x0,
                                           long long m, long long n, int d,
                                           int df, long long n_words, int rg) {
   extern __shared__ __bf16 smem[];
-  __bf16* xs[NSLICE];
-  __bf16* cs[NSLICE];
-  const __bf16* const xg[3] = {x0, x1, x2};
-  const __bf16* const cg[3] = {c0, c1, c2};
-#pragma unroll
-  for (int s = 0; s < NSLICE; s++) {
-    xs[s] = smem + s * 8192;
-    cs[s] = smem + (NSLICE + s) * 8192;
-  }
-
-  const int lane = threadIdx.x % RAFT_AMD_WAVE;
-  const int w = threadIdx.x / RAFT_AMD_WAVE;
-  const int wr = w >> 1, wc = w & 1;
-  long long rt_, ct_;
-  xcd_supertile_decode(rg, &rt_, &ct_);
-  if (rt_ * 128 >= m || ct_ * 128 >= n) return;  // super-tile ragged edge
-  const long long row0 = rt_ * 128;
-  const long long col0 = ct_ * 128;
-
+  MfmaTile t;
   f32x4 acc[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; a++)
-#pragma unroll
-    for (int b = 0; b < 4; b++) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  mfma_tile_kloop<NSLICE>(xg, cg, xs, cs, acc, row0, col0, d, m - 1, n - 1,
-                          wr, wc, lane);
+  if (!mfma_tile_prologue<128>(rg, m, n, t, acc)) return;
+  const int lane = t.lane, wr = t.wr, wc = t.wc;
+  const long long row0 = t.row0, col0 = t.col0;
+  mfma_tile_kloop<NSLICE>(p, smem, acc, t, m, n, d);
 
   // The K-loop LDS is dead (the loop ends on a barrier): reuse it for the
   // tile's [128][4] decision words and, when verifying, [128][4] band words.
@@ -199,25 +173,22 @@ void launch_eps_neighbors_l2sq(const void** xsl, const void** csl, const float* 
   const int cg = (int)((n + 1023) / 1024);
   dim3 grid((unsigned)((long long)rg * cg * 64));
   const size_t lds = (size_t)nslice * 2 * 8192 * sizeof(__bf16);
-  const __bf16* x0 = (const __bf16*)xsl[0];
-  const __bf16* x1 = (const __bf16*)(nslice > 1 ? xsl[1] : xsl[0]);
-  const __bf16* c0 = (const __bf16*)csl[0];
-  const __bf16* c1 = (const __bf16*)(nslice > 1 ? csl[1] : csl[0]);
+  const SlicePtrs p(xsl, csl, nslice);
   const bool verify = xf != nullptr;
   if (verify && (yf == nullptr || rechecked == nullptr))
     throw std::runtime_error("eps_neighbors_l2sq: verify needs xf, yf and a counter");
   const float lead2 = 2.f * lead, tail2 = 2.f * tail;
   if (nslice == 1 && !verify) {
     hipLaunchKernelGGL((eps_neighbors_l2sq_kernel<1, false>), grid, dim3(256), lds,
-                       stream, x0, x1, x0, c0, c1, c0, xn, yn, xf, yf, bitmap,
+                       stream, p, xn, yn, xf, yf, bitmap,
                        rechecked, eps2, lead2, tail2, m, n, d, df, n_words, rg);
   } else if (nslice == 1) {
     hipLaunchKernelGGL((eps_neighbors_l2sq_kernel<1, true>), grid, dim3(256), lds,
-                       stream, x0, x1, x0, c0, c1, c0, xn, yn, xf, yf, bitmap,
+                       stream, p, xn, yn, xf, yf, bitmap,
                        rechecked, eps2, lead2, tail2, m, n, d, df, n_words, rg);
   } else if (nslice == 2 && verify) {
     hipLaunchKernelGGL((eps_neighbors_l2sq_kernel<2, true>), grid, dim3(256), lds,
-                       stream, x0, x1, x0, c0, c1, c0, xn, yn, xf, yf, bitmap,
+                       stream, p, xn, yn, xf, yf, bitmap,
                        rechecked, eps2, lead2, tail2, m, n, d, df, n_words, rg);
   } else {
     throw std::runtime_error(

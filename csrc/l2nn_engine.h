@@ -6,20 +6,9 @@
 
 #include <string>
 
-namespace raft_amd {
+#include "slice_ptrs.h"
 
-// bf16 slice pointers of a launch; a missing slice aliases slice 0 (the
-// kernels never read it)
-struct SlicePtrs {
-  const __bf16* x[3];
-  const __bf16* c[3];
-  SlicePtrs(const void** xsl, const void** csl, int nslice) {
-    for (int s = 0; s < 3; s++) {
-      x[s] = (const __bf16*)xsl[s < nslice ? s : 0];
-      c[s] = (const __bf16*)csl[s < nslice ? s : 0];
-    }
-  }
-};
+namespace raft_amd {
 
 enum class L2nnEngine {
   Auto,        // "auto": environment overrides, then the measured defaults

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "slice_ptrs.h"
 
 namespace raft_amd {
 
@@ -76,6 +77,39 @@ __device__ __forceinline__ void xcd_supertile_decode(int rg, long long* rt,
   const int wc = cm ? (w & 7) : (w >> 3);
   *rt = (long long)(g % rg) * 8 + wr;
   *ct = (long long)(g / rg) * 8 + wc;
+}
+
+// Where a block and a wave of a TILE x TILE (128: 4 waves 2x2, 256: 8 waves
+// 2x4) kernel on the super-tiled grid stand. A wave owns TILE/2 rows x 64
+// columns: acc[TILE/32][4] fragments of 16 x 16.
+struct MfmaTile {
+  long long row0, col0;  // first row / column of the block's tile
+  int lane, wr, wc;      // lane, wave row, wave column
+};
+
+// Block prologue: decodes the tile, zeroes the accumulator. False on the
+// ragged super-tile edge, where the block has no tile and must return.
+template <int TILE>
+__device__ __forceinline__ bool mfma_tile_prologue(int rg, long long m, long long n,
+                                                   MfmaTile& t,
+                                                   f32x4 (&acc)[TILE / 32][4]) {
+  const unsigned w = threadIdx.x / RAFT_AMD_WAVE;
+  t.lane = threadIdx.x % RAFT_AMD_WAVE;
+  t.wr = w / (TILE / 64);
+  t.wc = w % (TILE / 64);
+  long long rt, ct;
+  xcd_supertile_decode(rg, &rt, &ct);
+  // the edge test stays on rt / ct, ahead of row0 / col0: testing the stored
+  // row0 / col0 instead measured 0.8% slower on the 2-slice eps-neighborhood
+  // kernel (596 vs 601 Gpairs/s at 200k x 200k x 128)
+  if (rt * TILE >= m || ct * TILE >= n) return false;
+  t.row0 = rt * TILE;
+  t.col0 = ct * TILE;
+#pragma unroll
+  for (int a = 0; a < TILE / 32; a++)
+#pragma unroll
+    for (int b = 0; b < 4; b++) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  return true;
 }
 
 template <int NSLICE>
@@ -162,6 +196,23 @@ __device__ __forceinline__ void mfma_tile_kloop(
     }
     __syncthreads();
   }
+}
+
+// The same K loop for a block's tile, with the slice tiles at the head of
+// `smem` (X slices, then C slices, 16 KiB each).
+template <int NSLICE>
+__device__ __forceinline__ void mfma_tile_kloop(const SlicePtrs& p, __bf16* smem,
+                                                f32x4 (&acc)[4][4], const MfmaTile& t,
+                                                long long m, long long n, int d) {
+  __bf16* xs[NSLICE];
+  __bf16* cs[NSLICE];
+#pragma unroll
+  for (int s = 0; s < NSLICE; s++) {
+    xs[s] = smem + s * 8192;
+    cs[s] = smem + (NSLICE + s) * 8192;
+  }
+  mfma_tile_kloop<NSLICE>(p.x, p.c, xs, cs, acc, t.row0, t.col0, d, m - 1, n - 1,
+                          t.wr, t.wc, t.lane);
 }
 
 // ---------------------------------------------------------------------------
@@ -370,6 +421,18 @@ __device__ __forceinline__ void mfma256_bk32_kloop(
   }
 #undef M256_GA
 #undef M256_GB
+}
+
+// setup + K loop for a block's ROWS x ROWS tile
+template <int NSLICE, int ROWS>
+__device__ __forceinline__ void mfma256_bk32_kloop(const SlicePtrs& p, __bf16* smem,
+                                                   f32x4 (&acc)[ROWS / 32][4],
+                                                   const MfmaTile& t, long long m,
+                                                   long long n, int d) {
+  Mfma256BK32 st;
+  mfma256_bk32_setup<ROWS>(st, t.row0, t.col0, d, m - 1, n - 1, t.wr, t.wc, t.lane);
+  mfma256_bk32_kloop<NSLICE, ROWS>(p.x[0], p.x[1], p.c[0], p.c[1], smem, st, acc,
+                                   d / 32);
 }
 
 // ---------------------------------------------------------------------------

@@ -23,7 +23,10 @@ void launch_pairwise_expanded_epilogue(float* g, const float* xa, const float* y
                                        long long m, long long n, int code, float d,
                                        hipStream_t s);
 // 128x128-tile MFMA kernel; out[ldo] row stride; epilogue fused into the
-// single non-temporal C write
+// single non-temporal C write. launch_pairwise_l2_mfma and
+// launch_pairwise_l2_filter apply the tuning environment
+// (docs/developer_guide.md); launch_pairwise_l2_mfma256 is the 256x256-tile
+// writer, nslice 1 or 2
 void launch_pairwise_l2_mfma(const void** xsl, const void** csl, const float* xn,
                              const float* yn, float* out, long long m, long long n,
                              int d, long long ldo, int nslice, bool sqrt_out, hipStream_t s);
