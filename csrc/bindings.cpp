@@ -70,6 +70,13 @@ void launch_make_blobs(float*, int*, const float*, long long, long long, int, fl
 template <typename T>
 void launch_csr_spmv(const int*, const int*, const T*, const T*, T*, long long,
                      long long, hipStream_t);
+// from sparse_pairwise.hip
+void launch_csr_row_stats(const int*, const float*, float*, long long, long long, int,
+                          float, hipStream_t);
+void launch_csr_pairwise(const int*, const int*, const float*, long long, long long,
+                         const int*, const int*, const float*, long long, long long,
+                         const float*, const float*, float*, long long, int, float, int,
+                         int, hipStream_t);
 // from kmeans.hip
 void launch_reduce_rows_by_key(const float*, const int*, float*, float*, long long,
                                long long, long long, int, hipStream_t);
@@ -299,6 +306,53 @@ torch::Tensor csr_spmv(torch::Tensor indptr, torch::Tensor indices, torch::Tenso
                                       cur_stream());
   }
   return y;
+}
+
+void check_csr_f32(const torch::Tensor& indptr, const torch::Tensor& indices,
+                   const torch::Tensor& values, int64_t n_rows, const char* name) {
+  TORCH_CHECK(indptr.is_cuda() && indices.is_cuda() && values.is_cuda(), name,
+              " must be on GPU");
+  TORCH_CHECK(indptr.scalar_type() == torch::kInt32 &&
+              indices.scalar_type() == torch::kInt32, name, " indices must be int32");
+  TORCH_CHECK(values.scalar_type() == torch::kFloat32, name, " values must be fp32");
+  TORCH_CHECK(indptr.is_contiguous() && indices.is_contiguous() && values.is_contiguous(),
+              name, " must be contiguous");
+  TORCH_CHECK(n_rows >= 0 && indptr.numel() == n_rows + 1, name,
+              " indptr must have n_rows + 1 entries");
+  TORCH_CHECK(indices.numel() == values.numel(), name, " indices / values differ in length");
+}
+
+// [n_rows, 2] fp32 row statistics of a CSR matrix for a sparse metric code
+torch::Tensor csr_row_stats(torch::Tensor indptr, torch::Tensor indices, torch::Tensor values,
+                            int64_t n_rows, int64_t metric, double p) {
+  check_csr_f32(indptr, indices, values, n_rows, "csr");
+  auto stats = torch::zeros({n_rows, 2}, values.options());
+  raft_amd::launch_csr_row_stats(indptr.data_ptr<int>(), values.data_ptr<float>(),
+                                 stats.data_ptr<float>(), n_rows, values.numel(),
+                                 (int)metric, (float)p, cur_stream());
+  return stats;
+}
+
+// [m, n] fp32 distances between the rows of two CSR matrices over d columns
+torch::Tensor csr_pairwise(torch::Tensor a_indptr, torch::Tensor a_indices,
+                           torch::Tensor a_values, int64_t m, torch::Tensor b_indptr,
+                           torch::Tensor b_indices, torch::Tensor b_values, int64_t n,
+                           torch::Tensor a_stats, torch::Tensor b_stats, int64_t d,
+                           int64_t metric, double p, int64_t strategy, int64_t param) {
+  check_csr_f32(a_indptr, a_indices, a_values, m, "a");
+  check_csr_f32(b_indptr, b_indices, b_values, n, "b");
+  TORCH_CHECK(a_stats.is_cuda() && a_stats.is_contiguous() && a_stats.numel() == 2 * m &&
+              a_stats.scalar_type() == torch::kFloat32, "a_stats must be [m, 2] fp32");
+  TORCH_CHECK(b_stats.is_cuda() && b_stats.is_contiguous() && b_stats.numel() == 2 * n &&
+              b_stats.scalar_type() == torch::kFloat32, "b_stats must be [n, 2] fp32");
+  auto out = torch::empty({m, n}, a_values.options());
+  raft_amd::launch_csr_pairwise(
+      a_indptr.data_ptr<int>(), a_indices.data_ptr<int>(), a_values.data_ptr<float>(), m,
+      a_values.numel(), b_indptr.data_ptr<int>(), b_indices.data_ptr<int>(),
+      b_values.data_ptr<float>(), n, b_values.numel(), a_stats.data_ptr<float>(),
+      b_stats.data_ptr<float>(), out.data_ptr<float>(), d, (int)metric, (float)p,
+      (int)strategy, (int)param, cur_stream());
+  return out;
 }
 
 torch::Tensor reduce_rows_by_key_sorted(torch::Tensor x, torch::Tensor perm,
@@ -1101,6 +1155,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("device"), pybind11::arg("gen") = 0);
   m.def("make_blobs", &make_blobs, "fused gaussian blob generator");
   m.def("csr_spmv", &csr_spmv, "CSR SpMV (sub-wave per row)");
+  m.def("csr_row_stats", &csr_row_stats,
+        "per-row statistics of a CSR matrix for a sparse pairwise metric");
+  m.def("csr_pairwise", &csr_pairwise,
+        "CSR x CSR pairwise distances (LDS-staged intersection contraction)");
   m.def("reduce_rows_by_key", &reduce_rows_by_key, "keyed row accumulation");
   m.def("reduce_rows_by_key_sorted", &reduce_rows_by_key_sorted,
         "keyed row accumulation over a key-sorted permutation");

@@ -17,6 +17,8 @@ from .op import (coo_sort, filter_zeros, dedupe_coo, slice_csr_rows, csr_row_op,
                  csr_diagonal, csr_set_diagonal)
 from .select_k import csr_select_k
 from .preprocessing import tfidf_transform, bm25_transform
+from .distance import sparse_pairwise_distance
+from .neighbors import sparse_knn
 from . import solver
 
 __all__ = [
@@ -26,5 +28,6 @@ __all__ = [
     "symmetrize_coo", "knn_graph_symmetrize", "csr_transpose", "csr_row_norm",
     "csr_degree", "csr_add",
     "coo_sort", "filter_zeros", "dedupe_coo", "slice_csr_rows", "csr_row_op",
-    "csr_select_k", "tfidf_transform", "bm25_transform", "solver",
+    "csr_select_k", "tfidf_transform", "bm25_transform",
+    "sparse_pairwise_distance", "sparse_knn", "solver",
 ]
