@@ -125,6 +125,14 @@ void launch_masked_l2nn_verify_repair(const float*, const float*, const float*,
                                       const float*, const float*, int*, unsigned int*,
                                       unsigned long long*, unsigned long long*,
                                       long long, int, int, float, float, hipStream_t);
+// from ivf_flat_scan.hip
+int ivf_flat_scan_max_qg(int);
+void launch_ivf_flat_scan(const void*, bool, const long long*, const long long*,
+                          const float*, const long long*, const long long*,
+                          const long long*, const long long*, const long long*,
+                          const long long*, const unsigned int*, long long, float*,
+                          long long, long long, long long, long long, long long,
+                          long long, int, int, int, int, hipStream_t);
 // from gemm_rocblas.cpp
 void gemm_bf16_f32_rowmajor(const void*, const void*, float*, long long, long long,
                             long long, float, void*);
@@ -911,6 +919,74 @@ void masked_l2nn_verify_repair(torch::Tensor x, torch::Tensor y, torch::Tensor x
       (int)df, (float)lead, (float)tail, cur_stream());
 }
 
+static const long long* ivf_i64(const torch::Tensor& t, long long numel, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kInt64 && t.is_contiguous() &&
+              t.numel() == numel,
+              "ivf_flat_scan: ", what, " must be a contiguous int64 GPU tensor of ",
+              numel, " elements");
+  return reinterpret_cast<const long long*>(t.data_ptr<int64_t>());
+}
+
+// IVF-Flat list scan of one query chunk into the ragged candidate buffer
+// `out` (filled in place; the caller pre-fills nothing: every padded row of
+// every probed list is written). The item / pair arrays are built on the
+// device by raft_amd/neighbors/ivf_flat.py; item_list.numel() is the grid's x
+// bound and n_items the device scalar that says how many items are real.
+void ivf_flat_scan(torch::Tensor data, torch::Tensor list_offsets, torch::Tensor indices,
+                   torch::Tensor queries, torch::Tensor item_list,
+                   torch::Tensor item_pair_begin, torch::Tensor item_pair_count,
+                   torch::Tensor n_items, torch::Tensor pair_query,
+                   torch::Tensor pair_out_off, c10::optional<torch::Tensor> filter_words,
+                   int64_t filter_bits, torch::Tensor out, int64_t metric, int64_t qg,
+                   int64_t y_split) {
+  TORCH_CHECK(data.is_cuda() && data.is_contiguous() && data.dim() == 1 &&
+              (data.scalar_type() == torch::kFloat32 ||
+               data.scalar_type() == torch::kBFloat16),
+              "ivf_flat_scan: data must be a flat contiguous fp32 or bf16 GPU tensor");
+  const bool bf16 = data.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(queries.is_cuda() && queries.is_contiguous() && queries.dim() == 2 &&
+              queries.scalar_type() == torch::kFloat32 && queries.size(1) >= 1,
+              "ivf_flat_scan: queries must be contiguous fp32 [q, d]");
+  const long long d = queries.size(1);
+  const long long v = bf16 ? 8 : 4;
+  const long long d_pad = (d + v - 1) / v * v;
+  TORCH_CHECK(d_pad <= 4096, "ivf_flat_scan: d_pad must be <= 4096");
+  const long long total_rows = indices.numel();
+  TORCH_CHECK(total_rows % 64 == 0 && data.numel() == total_rows * d_pad,
+              "ivf_flat_scan: data must hold indices.numel() rows of d_pad elements "
+              "and the row count must be a multiple of 64");
+  const long long n_lists = list_offsets.numel() - 1;
+  TORCH_CHECK(n_lists >= 1, "ivf_flat_scan: list_offsets must be int64 [n_lists + 1]");
+  const long long n_pairs = pair_query.numel();
+  const long long max_items = item_list.numel();
+  const long long* lo = ivf_i64(list_offsets, n_lists + 1, "list_offsets");
+  const long long* idx = ivf_i64(indices, total_rows, "indices");
+  const long long* il = ivf_i64(item_list, max_items, "item_list");
+  const long long* ib = ivf_i64(item_pair_begin, max_items, "item_pair_begin");
+  const long long* ic = ivf_i64(item_pair_count, max_items, "item_pair_count");
+  const long long* ni = ivf_i64(n_items, 1, "n_items");
+  const long long* pq = ivf_i64(pair_query, n_pairs, "pair_query");
+  const long long* po = ivf_i64(pair_out_off, n_pairs, "pair_out_off");
+  TORCH_CHECK(out.is_cuda() && out.is_contiguous() && out.dim() == 1 &&
+              out.scalar_type() == torch::kFloat32,
+              "ivf_flat_scan: out must be a flat contiguous fp32 GPU tensor");
+  const unsigned int* fw = nullptr;
+  if (filter_words.has_value()) {
+    const torch::Tensor& f = filter_words.value();
+    TORCH_CHECK(f.is_cuda() && f.scalar_type() == torch::kInt32 && f.is_contiguous() &&
+                f.dim() == 1 && filter_bits >= 0 && f.numel() * 32 >= filter_bits,
+                "ivf_flat_scan: filter must be int32 words covering filter_bits");
+    fw = reinterpret_cast<const unsigned int*>(f.data_ptr<int>());
+  }
+  TORCH_CHECK(qg >= 1 && qg <= raft_amd::ivf_flat_scan_max_qg((int)d_pad),
+              "ivf_flat_scan: qg too large for d_pad");
+  raft_amd::launch_ivf_flat_scan(
+      data.data_ptr(), bf16, lo, idx, queries.data_ptr<float>(), il, ib, ic, ni, pq, po,
+      fw, filter_bits, out.data_ptr<float>(), out.numel(), n_lists, total_rows,
+      queries.size(0), n_pairs, max_items, (int)d, (int)metric, (int)qg, (int)y_split,
+      cur_stream());
+}
+
 void bitmap_row_degrees(torch::Tensor bitmap, torch::Tensor deg) {
   const unsigned int* bm = bitmap_words(bitmap, "bitmap_row_degrees");
   TORCH_CHECK(deg.is_cuda() && deg.scalar_type() == torch::kInt64 &&
@@ -1303,6 +1379,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("x_group"), pybind11::arg("y_rank"), pybind11::arg("dmin"), pybind11::arg("amin"),
         pybind11::arg("dmin2"), pybind11::arg("yn_max"), pybind11::arg("rescanned"),
         pybind11::arg("lead") = 0x1p-13, pybind11::arg("tail") = 0x1p-18);
+  m.def("ivf_flat_scan", &ivf_flat_scan,
+        "IVF-Flat list-major scan of the probed lists into a ragged candidate buffer",
+        pybind11::arg("data"), pybind11::arg("list_offsets"), pybind11::arg("indices"),
+        pybind11::arg("queries"), pybind11::arg("item_list"),
+        pybind11::arg("item_pair_begin"), pybind11::arg("item_pair_count"),
+        pybind11::arg("n_items"), pybind11::arg("pair_query"),
+        pybind11::arg("pair_out_off"), pybind11::arg("filter_words"),
+        pybind11::arg("filter_bits"), pybind11::arg("out"), pybind11::arg("metric"),
+        pybind11::arg("qg"), pybind11::arg("y_split"));
+  m.def("ivf_flat_scan_max_qg", [](int64_t d_pad) {
+    return (int64_t)raft_amd::ivf_flat_scan_max_qg((int)d_pad);
+  }, "largest query-group size whose staged queries fit the scan kernel's LDS");
   m.def("bitmap_row_degrees", &bitmap_row_degrees,
         "per-row popcount of a row-padded bitmap into an int64 vector");
   m.def("bitmap_rows_to_csr", &bitmap_rows_to_csr,

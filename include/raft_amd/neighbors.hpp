@@ -92,4 +92,31 @@ void launch_masked_l2nn_verify_repair(const float* x, const float* y, const floa
                                       int n, int df, float lead, float tail,
                                       hipStream_t s);
 
+// IVF-Flat list scan (csrc/ivf_flat_scan.hip): distances from queries to the
+// rows of the lists they probe, list-major. data is the interleaved index
+// buffer (fp32, or bf16 with data_bf16): rows in groups of 64, 16-byte chunks,
+// d padded to the chunk; list_offsets[n_lists + 1] in rows (multiples of 64);
+// indices[total_rows] dataset ids, -1 in pad slots. Work item i < *n_items
+// (a DEVICE scalar; the grid's x size max_items is an upper bound) scans list
+// item_list[i] for the item_pair_count[i] <= qg sorted pairs starting at
+// item_pair_begin[i]; sorted pair p belongs to query row pair_query[p] of
+// queries [n_queries, d] and writes its list's padded rows at
+// out[pair_out_off[p] + row]. Pad rows and rows whose id has a clear bit in
+// filter_words (nullptr: no filter; ids >= filter_bits are rejected) get +inf
+// (-inf for inner product). metric: 0 squared L2 (unexpanded sum), 1 its
+// square root, 2 inner product. qg in {4, 8, 16, 32} with
+// qg <= ivf_flat_scan_max_qg(d_pad); y_split blocks share a list's groups.
+int ivf_flat_scan_max_qg(int d_pad);
+void launch_ivf_flat_scan(const void* data, bool data_bf16,
+                          const long long* list_offsets, const long long* indices,
+                          const float* queries, const long long* item_list,
+                          const long long* item_pair_begin,
+                          const long long* item_pair_count, const long long* n_items,
+                          const long long* pair_query, const long long* pair_out_off,
+                          const unsigned int* filter_words, long long filter_bits,
+                          float* out, long long out_numel, long long n_lists,
+                          long long total_rows, long long n_queries, long long n_pairs,
+                          long long max_items, int d, int metric, int qg, int y_split,
+                          hipStream_t s);
+
 }  // namespace raft_amd
