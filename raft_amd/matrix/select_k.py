@@ -30,16 +30,38 @@ class SelectAlgo(Enum):
     TORCH = "torch"   # vendor topk (used for cross-checking, like the cub-sort check)
 
 
+def slab_order(vals: torch.Tensor, select_min: bool, pad: torch.Tensor = None):
+    """Column order that sorts each row of a small [batch, k] slab by the
+    select_k ordering rule: numeric order (reversed for select-max), then
+    every NaN, then the slots flagged in `pad`. torch's own sort cannot be
+    asked for this: it puts NaN first when descending, and on the GPU a
+    sign-bit NaN first when ascending."""
+    rank = torch.isnan(vals).to(torch.uint8)
+    if pad is not None:
+        rank = torch.where(pad, torch.full_like(rank, 2), rank)
+    key = torch.where(rank > 0, torch.zeros_like(vals),
+                      vals if select_min else -vals)
+    by_key = torch.argsort(key, dim=1, stable=True)
+    by_rank = torch.argsort(torch.gather(rank, 1, by_key), dim=1, stable=True)
+    return torch.gather(by_key, 1, by_rank)
+
+
 def select_k(x: torch.Tensor, k: int, select_min: bool = True,
              algo: SelectAlgo = SelectAlgo.AUTO, sorted: bool = True):
     """Per-row k smallest (or largest) values of a [batch, len] matrix.
 
     Returns (values [batch,k], indices [batch,k] int64).
 
-    NaN semantics: both native engines canonicalize NaN (any sign/payload) to
-    the maximum ordinal, so NaN orders after every finite value and +/-inf in
-    BOTH selection directions; NaNs are only selected when a row has fewer
-    than k non-NaN values, and then they carry their real in-range indices.
+    Ordering rule (every native GPU route: warpsort, radix, the two-level
+    split, the generic engine and the half-precision widen route): values
+    compare numerically, reversed for select_min=False, with -0.0 == +0.0;
+    NaN of any sign or payload orders after every finite value and +/-inf in
+    BOTH selection directions. NaNs are only selected when a row has fewer
+    than k non-NaN values, and then they come last and carry their real
+    in-range indices. Indices within a row are distinct and x[row, idx] is
+    bitwise the returned value. With sorted=False the same k entries come
+    back in any order. The vendor route (fp32, 64 < k, len <= 4096) and the
+    CPU path are torch.topk and keep its NaN order.
     """
     assert x.dim() == 2
     batch, n = x.shape
@@ -54,9 +76,11 @@ def select_k(x: torch.Tensor, k: int, select_min: bool = True,
         # engine's histogram + 2 filter re-reads (measured [8192 x 100k]
         # k=64 bf16: generic 5.5 ms / torch.topk 3.7 -> this route 3.35).
         # bf16->fp32 is exact, so selection and values are unchanged.
-        vals, idx = select_k(x.float(), k, select_min=select_min, algo=algo,
-                             sorted=sorted)
-        return vals.to(x.dtype), idx
+        _, idx = select_k(x.float(), k, select_min=select_min, algo=algo,
+                          sorted=sorted)
+        # gather instead of narrowing the fp32 values back: a float
+        # conversion rewrites NaN payloads
+        return torch.gather(x, 1, idx), idx
 
     if (on_gpu(x) and algo != SelectAlgo.TORCH
             and (x.dtype in (torch.float64, torch.bfloat16, torch.float16)
@@ -68,7 +92,7 @@ def select_k(x: torch.Tensor, k: int, select_min: bool = True,
         vals, idx = ext.select_k_generic(x.contiguous(), None, k=k,
                                          select_min=bool(select_min))
         if sorted:
-            order = torch.argsort(vals, dim=1, descending=not select_min)
+            order = slab_order(vals, select_min)
             vals = torch.gather(vals, 1, order)
             idx = torch.gather(idx, 1, order)
         return vals, idx
@@ -99,29 +123,27 @@ def select_k(x: torch.Tensor, k: int, select_min: bool = True,
             while batch * s * 2 <= 2048 and (n // (s * 2)) >= max(4 * k, 4096):
                 s *= 2
             if s > 1:
-                seg = -(-n // s)          # ceil
-                pad = seg * s - n
-                if pad:
-                    fill = float("inf") if select_min else float("-inf")
-                    xp = torch.cat([x, torch.full((batch, pad), fill, dtype=x.dtype,
-                                                  device=x.device)], dim=1)
-                else:
-                    xp = x
-                segs = xp.reshape(batch * s, seg).contiguous()
+                # segment the first s*floor(n/s) columns; the < s columns
+                # left over join the candidates with their own indices, so
+                # no fabricated value or index can reach the final select
+                seg = n // s
+                main = seg * s
+                segs = x[:, :main].reshape(batch * s, seg).contiguous()
                 sv, si = ext.select_k(segs, min(k, seg), bool(select_min), 0, False)
                 kk = sv.shape[1]
-                cand_v = sv.reshape(batch, s * kk)
                 base = (torch.arange(s, device=x.device, dtype=torch.int64) * seg)
+                cand_v = sv.reshape(batch, s * kk)
                 cand_i = (si.to(torch.int64).reshape(batch, s, kk)
                           + base.view(1, s, 1)).reshape(batch, s * kk)
+                if main < n:
+                    tail_i = torch.arange(main, n, device=x.device,
+                                          dtype=torch.int64)
+                    cand_v = torch.cat([cand_v, x[:, main:]], dim=1)
+                    cand_i = torch.cat([cand_i, tail_i.expand(batch, n - main)],
+                                       dim=1)
                 fv, fpos = ext.select_k(cand_v.contiguous(), k, bool(select_min),
                                         0, bool(sorted))
-                gi = torch.gather(cand_i, 1, fpos.to(torch.int64))
-                # padded +/-inf slots carry fabricated indices base+pos >= n;
-                # they are only selected when a row has < k real candidates —
-                # clamp so callers never see an out-of-range index
-                gi.clamp_(max=n - 1)
-                return fv, gi
+                return fv, torch.gather(cand_i, 1, fpos.to(torch.int64))
         algo_code = {SelectAlgo.AUTO: 0, SelectAlgo.RADIX: 1, SelectAlgo.WARPSORT: 2}[algo]
         if algo == SelectAlgo.AUTO and k <= 64 and batch >= 2048 and n >= 100000:
             # measured on gfx950 (benchmarks 2026-09): the wave-register

@@ -19,7 +19,13 @@ from .types import CSR
 
 def csr_select_k(a: CSR, k: int, select_min: bool = True):
     """Per-row top-k of CSR values. Returns (vals [n_rows,k], col_idx [n_rows,k]);
-    missing slots hold +inf/-inf and index -1."""
+    missing slots hold +inf/-inf and index -1.
+
+    Ordering rule on the GPU (the one of raft_amd.matrix.select_k): each row
+    comes back in numeric order, reversed for select_min=False; a NaN entry
+    of the row orders after every number and +/-inf in both directions, and
+    the pads of a row shorter than k come after every real entry, NaN
+    included. The CPU path densifies and keeps torch.topk's NaN order."""
     if a.values.is_cuda and a.values.dtype in (torch.float32, torch.float64,
                                                torch.bfloat16, torch.float16):
         from raft_amd._ext import require_ext
@@ -32,12 +38,10 @@ def csr_select_k(a: CSR, k: int, select_min: bool = True):
         flat = (row_off[:-1].unsqueeze(1) + pos.clamp_min(0)).reshape(-1)
         cols = a.indices.to(torch.int64)[flat].reshape(pos.shape)
         cols = torch.where(valid, cols, torch.full_like(cols, -1))
-        # sort each row (generic kernel output is unsorted)
-        order = torch.argsort(torch.where(valid, vals,
-                                          torch.full_like(vals, float("inf")
-                                                          if select_min else
-                                                          float("-inf"))),
-                              dim=1, descending=not select_min)
+        # sort each row (generic kernel output is unsorted): numbers, then
+        # the row's NaNs, then the pads
+        from raft_amd.matrix.select_k import slab_order
+        order = slab_order(vals, select_min, pad=~valid)
         return torch.gather(vals, 1, order), torch.gather(cols, 1, order)
     pad = float("inf") if select_min else float("-inf")
     lengths = (a.indptr[1:] - a.indptr[:-1]).to(torch.int64)

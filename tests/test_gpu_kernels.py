@@ -353,6 +353,10 @@ class TestSelectKGpu:
             assert idx[r].unique().numel() == 64
 
     def test_duplicates_at_kth(self, dev, ext):
+        """k = 100 > 64 at n = 1000 <= 4096 is dispatched to the vendor top-k
+        (torch.topk), as are (128, 512, 256) and (16, 2048, 1024) above: no
+        native kernel runs here. Ties at the k-th value on the native engines
+        are covered in tests/test_gpu_select_k.py."""
         from raft_amd.matrix import select_k
         x = torch.zeros(3, 1000, device=dev)
         x[:, :50] = -1.0  # 50 identical minima, k straddles them
