@@ -14,6 +14,7 @@ namespace {
 // A/B tuning switches, read once per process (docs/developer_guide.md)
 struct L2nnEnv {
   char mode_2d, mode_256;  // '0' off, '1' wherever the shape allows, else auto
+  char mode_xreg;          // '0' off, '1' on, else the measured default
   char w8;                 // '0' off, '2' for every nslice, else 3-slice only
   int gt;                  // 1, 2, 4 or 8; 0 = per-nslice default
   bool bk32, adirect, db, phased, persist;
@@ -28,6 +29,7 @@ const L2nnEnv& l2nn_env() {
     L2nnEnv v;
     v.mode_2d = first("RAFT_AMD_L2NN_2D");
     v.mode_256 = first("RAFT_AMD_L2NN_256");
+    v.mode_xreg = first("RAFT_AMD_L2NN_XREG");
     v.w8 = first("RAFT_AMD_L2NN_W8");
     const char* g = getenv("RAFT_AMD_L2NN_GT");
     v.gt = g ? atoi(g) : 0;
@@ -44,7 +46,11 @@ const L2nnEnv& l2nn_env() {
 
 constexpr const char* kEngineNames[] = {"auto",      "v1",      "v1_db", "v1_phased",
                                         "2d",        "2d_phased", "2d_bk32", "2d_ad",
-                                        "256",       "w8",      "persist"};
+                                        "256",       "w8",      "persist", "2d_xreg"};
+
+// auto picks 2d_xreg over 2d where both fit: 5.47 against 7.61 ms at
+// 10M x 256 k=1024, one process, alternating
+constexpr bool kXregDefault = true;
 
 bool is_2d(L2nnEngine e) {
   return e == L2nnEngine::TwoD || e == L2nnEngine::TwoDPhased ||
@@ -75,6 +81,10 @@ const char* l2nn_engine_violation(L2nnEngine e, int nslice, int n, int d) {
     case L2nnEngine::Persist:
       if (d > 256) return "d must be at most 256 (X stays in LDS)";
       return nullptr;
+    case L2nnEngine::TwoDXreg:
+      if (nslice != 1) return "nslice must be 1";
+      if (d > 256) return "d must be at most 256 (X stays in registers)";
+      return nullptr;
     default:
       return nullptr;
   }
@@ -87,6 +97,13 @@ const char* l2nn_engine_violation(L2nnEngine e, int nslice, int n, int d) {
 bool l2nn_2d_wanted(int nslice, long long m, int n) {
   const char mode = l2nn_env().mode_2d;
   return mode != '0' && nslice <= 2 && (mode == '1' || (n >= 512 && m >= 1000000));
+}
+
+// 2d_xreg takes the 1-slice d <= 256 shapes from 2d where 2d is wanted;
+// RAFT_AMD_L2NN_XREG=0 gives them back, =1 is the default spelled out
+bool l2nn_xreg_wanted() {
+  const char mode = l2nn_env().mode_xreg;
+  return mode != '0' && (mode == '1' || kXregDefault);
 }
 
 // w8 wins only for NSLICE=3 (staging-bound: halved X re-reads beat the lost
@@ -110,6 +127,7 @@ L2nnEngine l2nn_auto_engine(int nslice, long long m, int n, int d) {
     // 10M x 1024 d=256). Kept as the base for future schedule work.
     if (env.mode_256 == '1' && fits(L2nnEngine::E256)) return L2nnEngine::E256;
     if (l2nn_2d_wanted(nslice, m, n)) {
+      if (l2nn_xreg_wanted() && fits(L2nnEngine::TwoDXreg)) return L2nnEngine::TwoDXreg;
       if (env.bk32) return L2nnEngine::TwoDBk32;
       if (env.adirect) return L2nnEngine::TwoDAd;
       return env.phased && nslice == 2 ? L2nnEngine::TwoDPhased : L2nnEngine::TwoD;
@@ -156,6 +174,15 @@ L2nnPlan l2nn_resolve_engine(int nslice, long long m, int n, int d,
     while (gt > 1 && tiles % gt != 0) gt >>= 1;
     plan.gt = gt;
     plan.n_groups = tiles / gt;
+  } else if (plan.engine == L2nnEngine::TwoDXreg) {
+    // same rule as the 1-slice 2d default; a single group writes the result
+    // itself and needs no partials
+    if (gt == 0) gt = l2nn_env().gt;
+    if (gt == 0) gt = 8;
+    const int tiles = n / 128;
+    while (gt > 1 && tiles % gt != 0) gt >>= 1;
+    plan.gt = gt;
+    plan.n_groups = tiles / gt > 1 ? tiles / gt : 0;
   } else if (plan.engine == L2nnEngine::E256) {
     plan.n_groups = n / 256;
   }
@@ -171,6 +198,8 @@ void launch_fused_l2nn(const L2nnPlan& plan, const void** xsl, const void** csl,
   if (is_2d(plan.engine))
     launch_l2nn_2d(p, xn, cn, pd, pd2, pi, dmin, amin, dmin2, m, n, d, nslice,
                    plan.engine, plan.gt, stream);
+  else if (plan.engine == L2nnEngine::TwoDXreg)
+    launch_l2nn_xreg(p, xn, cn, pd, pd2, pi, dmin, amin, dmin2, m, n, d, plan.gt, stream);
   else if (plan.engine == L2nnEngine::E256)
     launch_l2nn_256(p, xn, cn, pd, pd2, pi, dmin, amin, dmin2, m, n, d, nslice, stream);
   else if (plan.engine == L2nnEngine::W8)

@@ -112,7 +112,16 @@ __global__ void reduce_rows_by_key_sorted_kernel(const float* __restrict__ x,
 // VEC4: lane-contiguous column map col(j) = (j/4)*256 + lane*4 + j%4 so each
 // lane's 4-column chunk loads as ONE dwordx4 (wave covers 1024 B/chunk);
 // requires d % 4 == 0. Otherwise the classic col(j) = j*64 + lane scalar map.
-template <int MAX_DREG, bool VEC4>
+// R: rows in flight per wave. A wave walks its chunk in batches of R rows:
+// first the R perm / key loads, then the R per-row scalars, then all R row
+// loads, and only then the per-row work, row by row in the original order.
+// One row at a time (a dependent perm load, a 1 KiB row load, a 6-step wave
+// reduction, strictly serial) left 8 MiB in flight across the chip and the
+// kernel at 3.5 TB/s. Per wave every floating-point add and every write
+// keeps its order, so results move only with the atomic order between waves.
+// launch bounds: the waves per SIMD each variant compiles to without scratch
+template <int MAX_DREG, bool VEC4, int R>
+__launch_bounds__(256, MAX_DREG == 4 ? (R <= 2 ? 8 : 5) : (R == 1 ? 6 : 4))
 __global__ void kmeans_update_verify_kernel(
     const float* __restrict__ x, const int* __restrict__ perm,
     const int* __restrict__ keys_sorted, const float* __restrict__ c,
@@ -130,7 +139,7 @@ __global__ void kmeans_update_verify_kernel(
   const long long stop = min(start + chunk, n_rows);
   const float cn_max = *cn_max_p;
 
-  float acc[MAX_DREG], creg[MAX_DREG], xv[MAX_DREG];
+  float acc[MAX_DREG], creg[MAX_DREG];
 #pragma unroll
   for (int j = 0; j < MAX_DREG; j++) acc[j] = 0.f;
   int cur_key = -1;
@@ -181,76 +190,144 @@ __global__ void kmeans_update_verify_kernel(
     run_len = 0;
   };
 
-  for (long long i = start; i < stop; i++) {
-    const long long row = perm[i];
-    const int key = keys_sorted[i];
+  // the three steps of one row, its operands already in registers
+  auto enter_key = [&](int key) {
     if (key != cur_key) {
       flush();
       cur_key = key;
       load_row(c + (long long)key * d, creg);
     }
-    const float* rp = x + row * d;
-    load_row(rp, xv);
-    const float xnr = xn[row];
-    const float margin = dmin2[row] - dmin[row];
-    const float bound = 2.f * (lead * sqrtf(fmaxf(xnr * cn_max, 0.f)) +
-                               tail * (xnr + cn_max));
-    if (margin < bound) {
-      // exact rescan over all centroids (rare: near-ties only)
-      float bestv = INFINITY;
-      int besti = 0;
-      for (int jc = 0; jc < n_centroids; jc++) {
-        const float* cp = c + (long long)jc * d;
-        float a = 0.f;
-        #pragma unroll
+  };
+  // exact fp32 refinement of the chosen distance (creg is run-resident)
+  auto refine = [&](long long row, const float (&xv)[MAX_DREG]) {
+    float a = 0.f;
+    #pragma unroll
     for (int j = 0; j < MAX_DREG; j++) {
-          const long long col = colmap(j);
-          if (col < d) {
-            const float diff = xv[j] - cp[col];
-            a += diff * diff;
-          }
-        }
-        a = wave_reduce_sum(a);
-        if (a < bestv) { bestv = a; besti = jc; }
-      }
-      if (lane == 0) {
-        dmin[row] = bestv;
-        amin[row] = besti;
-      }
-      local_inertia += (double)bestv;
-      if (besti == cur_key) {
-        #pragma unroll
+      const float diff = xv[j] - creg[j];
+      a += diff * diff;
+    }
+    a = wave_reduce_sum(a);
+    if (lane == 0) dmin[row] = a;
+    local_inertia += (double)a;
+    #pragma unroll
     for (int j = 0; j < MAX_DREG; j++) acc[j] += xv[j];
-        run_len++;
-      } else {
-        // reassigned: direct atomics into the new cluster
-        float* sp = sums + (long long)besti * d;
-        #pragma unroll
-    for (int j = 0; j < MAX_DREG; j++) {
-          const long long col = colmap(j);
-          if (col < d) atomicAdd(&sp[col], xv[j]);
-        }
-        if (lane == 0) atomicAdd(&counts[besti], 1.f);
-      }
-    } else {
-      // exact fp32 refinement of the chosen distance (creg is run-resident)
+    run_len++;
+  };
+  // exact rescan over all centroids (rare: near-ties only)
+  auto rescan = [&](long long row, const float (&xv)[MAX_DREG]) {
+    float bestv = INFINITY;
+    int besti = 0;
+    for (int jc = 0; jc < n_centroids; jc++) {
+      const float* cp = c + (long long)jc * d;
       float a = 0.f;
       #pragma unroll
-    for (int j = 0; j < MAX_DREG; j++) {
-        const float diff = xv[j] - creg[j];
-        a += diff * diff;
+      for (int j = 0; j < MAX_DREG; j++) {
+        const long long col = colmap(j);
+        if (col < d) {
+          const float diff = xv[j] - cp[col];
+          a += diff * diff;
+        }
       }
       a = wave_reduce_sum(a);
-      if (lane == 0) dmin[row] = a;
-      local_inertia += (double)a;
+      if (a < bestv) { bestv = a; besti = jc; }
+    }
+    if (lane == 0) {
+      dmin[row] = bestv;
+      amin[row] = besti;
+    }
+    local_inertia += (double)bestv;
+    if (besti == cur_key) {
       #pragma unroll
-    for (int j = 0; j < MAX_DREG; j++) acc[j] += xv[j];
+      for (int j = 0; j < MAX_DREG; j++) acc[j] += xv[j];
       run_len++;
+    } else {
+      // reassigned: direct atomics into the new cluster
+      float* sp = sums + (long long)besti * d;
+      #pragma unroll
+      for (int j = 0; j < MAX_DREG; j++) {
+        const long long col = colmap(j);
+        if (col < d) atomicAdd(&sp[col], xv[j]);
+      }
+      if (lane == 0) atomicAdd(&counts[besti], 1.f);
+    }
+  };
+
+  for (long long i0 = start; i0 < stop; i0 += R) {
+    // a short last batch re-reads the chunk's last row into the spare slots
+    // (rows of a permutation are distinct: nothing below writes what a later
+    // slot of the batch has read) and processes only the real ones
+    long long row[R];
+    int key[R];
+    float xnr[R], margin[R], xv[R][MAX_DREG];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      const long long i = min(i0 + r, stop - 1);
+      row[r] = perm[i];
+      key[r] = keys_sorted[i];
+    }
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      xnr[r] = xn[row[r]];
+      margin[r] = dmin2[row[r]] - dmin[row[r]];
+    }
+#pragma unroll
+    for (int r = 0; r < R; r++) load_row(x + row[r] * d, xv[r]);
+    bool near[R], any_near = false;
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+      const float bound = 2.f * (lead * sqrtf(fmaxf(xnr[r] * cn_max, 0.f)) +
+                                 tail * (xnr[r] + cn_max));
+      near[r] = margin[r] < bound;
+      any_near |= near[r];
+    }
+    if constexpr (R == 1) {
+      enter_key(key[0]);
+      if (near[0]) rescan(row[0], xv[0]);
+      else refine(row[0], xv[0]);
+    } else if (!any_near) {
+#pragma unroll
+      for (int r = 0; r < R; r++)
+        if (i0 + r < stop) {
+          enter_key(key[r]);
+          refine(row[r], xv[r]);
+        }
+    } else {
+      // a batch with a near-tie: ONE rolled copy of the row steps (the rescan
+      // unrolled R times costs the registers that keep 8 waves per SIMD),
+      // slot r picked by wave-uniform selects; same order, same arithmetic
+#pragma unroll 1
+      for (int r = 0; r < R && i0 + r < stop; r++) {
+        long long row_r = row[0];
+        int key_r = key[0];
+        bool near_r = near[0];
+        float xv_r[MAX_DREG];
+#pragma unroll
+        for (int j = 0; j < MAX_DREG; j++) xv_r[j] = xv[0][j];
+#pragma unroll
+        for (int q = 1; q < R; q++)
+          if (r == q) {
+            row_r = row[q];
+            key_r = key[q];
+            near_r = near[q];
+#pragma unroll
+            for (int j = 0; j < MAX_DREG; j++) xv_r[j] = xv[q][j];
+          }
+        enter_key(key_r);
+        if (near_r) rescan(row_r, xv_r);
+        else refine(row_r, xv_r);
+      }
     }
   }
   flush();
   if (inertia_acc && lane == 0) atomicAdd(inertia_acc, (float)local_inertia);
 }
+
+// rows in flight per wave, per registers-per-row variant. Measured (round 3,
+// BASELINE.md): at 4 registers 2 rows keep 64 VGPRs and 8 waves per SIMD and
+// win; 4 rows (83 VGPRs, 5 waves) and a software-pipelined next-row load both
+// lose to the parent. At 16 registers 2 rows (4 waves) beat 1 row (6 waves).
+constexpr int KMUV_ROWS_D4 = 2;
+constexpr int KMUV_ROWS_D16 = 2;
 
 void launch_kmeans_update_verify(const float* x, const int* perm,
                                  const int* keys_sorted, const float* c,
@@ -265,11 +342,11 @@ void launch_kmeans_update_verify(const float* x, const int* perm,
   if (chunk < 8) chunk = 8;
   const long long n_waves = (n_rows + chunk - 1) / chunk;
   const int grid = (int)((n_waves * RAFT_AMD_WAVE + 255) / 256);
-#define KMUV_LAUNCH(MD, V4)                                                   \
-  hipLaunchKernelGGL((kmeans_update_verify_kernel<MD, V4>), dim3(grid),       \
-                     dim3(256), 0, stream, x, perm, keys_sorted, c, xn, dmin, \
-                     amin, dmin2, cn_max_dev, sums, counts, inertia_acc,      \
-                     n_rows, d, n_centroids, chunk, lead, tail)
+#define KMUV_LAUNCH(MD, V4)                                                    \
+  hipLaunchKernelGGL((kmeans_update_verify_kernel<MD, V4, MD == 4 ? KMUV_ROWS_D4 : KMUV_ROWS_D16>), \
+                     dim3(grid), dim3(256), 0, stream, x, perm, keys_sorted, c, \
+                     xn, dmin, amin, dmin2, cn_max_dev, sums, counts,          \
+                     inertia_acc, n_rows, d, n_centroids, chunk, lead, tail)
   // VEC4 keeps only d/4 lanes loading (4 cols per lane): require d >= 256
   // so all 64 lanes stay active
   const bool v4 = (d % 4 == 0) && d >= 256;
