@@ -158,8 +158,18 @@ void check_f32_2d(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.dim() == 2, name, " must be 2D");
 }
 
+void check_reduce_input(const torch::Tensor& x, int64_t op, int64_t reduced) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2,
+              "x must be a contiguous 2D GPU tensor");
+  TORCH_CHECK(x.scalar_type() == torch::kFloat32 || x.scalar_type() == torch::kFloat64,
+              "x must be float32 or float64");
+  TORCH_CHECK(op >= 0 && op <= 5, "bad op code ", op);
+  // sums over an empty axis are zeros; min/max have no identity to return
+  TORCH_CHECK(op <= 2 || reduced > 0, "min/max reduction over an empty axis");
+}
+
 torch::Tensor reduce_rows(torch::Tensor x, int64_t op) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2);
+  check_reduce_input(x, op, x.dim() == 2 ? x.size(1) : 1);
   auto out = torch::empty({x.size(0)}, x.options());
   auto s = cur_stream();
   const long long m = x.size(0), d = x.size(1);
@@ -177,7 +187,7 @@ torch::Tensor reduce_rows(torch::Tensor x, int64_t op) {
 }
 
 torch::Tensor reduce_cols(torch::Tensor x, int64_t op) {
-  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2);
+  check_reduce_input(x, op, x.dim() == 2 ? x.size(0) : 1);
   auto out = torch::empty({x.size(1)}, x.options());
   auto s = cur_stream();
   const long long m = x.size(0), d = x.size(1);
@@ -205,6 +215,9 @@ torch::Tensor rows_sqnorm_bf16(torch::Tensor x) {
 
 torch::Tensor row_argmin(torch::Tensor x) {
   check_f32_2d(x, "x");
+  TORCH_CHECK(x.scalar_type() == torch::kFloat32, "x must be float32");
+  TORCH_CHECK(x.size(1) > 0 && x.size(1) <= 2147483647LL,
+              "argmin needs 1 <= row length < 2^31");
   auto out = torch::empty({x.size(0)}, x.options().dtype(torch::kInt32));
   raft_amd::launch_row_argmin(x.data_ptr<float>(), out.data_ptr<int>(), x.size(0),
                               x.size(1), cur_stream());
@@ -213,6 +226,7 @@ torch::Tensor row_argmin(torch::Tensor x) {
 
 torch::Tensor row_normalize_l2(torch::Tensor x, double eps) {
   check_f32_2d(x, "x");
+  TORCH_CHECK(x.scalar_type() == torch::kFloat32, "x must be float32");
   auto out = torch::empty_like(x);
   raft_amd::launch_row_normalize_l2(x.data_ptr<float>(), out.data_ptr<float>(),
                                     x.size(0), x.size(1), (float)eps, cur_stream());
@@ -298,9 +312,26 @@ std::tuple<torch::Tensor, torch::Tensor> make_blobs(int64_t n_rows, int64_t d,
 }
 
 torch::Tensor csr_spmv(torch::Tensor indptr, torch::Tensor indices, torch::Tensor values,
-                       torch::Tensor x, int64_t n_rows) {
-  TORCH_CHECK(indptr.is_cuda() && indptr.scalar_type() == torch::kInt32);
-  TORCH_CHECK(indices.is_cuda() && indices.scalar_type() == torch::kInt32);
+                       torch::Tensor x, int64_t n_rows, int64_t n_cols) {
+  // every tensor becomes a raw device pointer below: reject anything the
+  // kernel could not dereference (column ids are the caller's contract)
+  TORCH_CHECK(indptr.is_cuda() && indptr.scalar_type() == torch::kInt32 &&
+              indptr.is_contiguous(), "indptr must be contiguous int32 on GPU");
+  TORCH_CHECK(indices.is_cuda() && indices.scalar_type() == torch::kInt32 &&
+              indices.is_contiguous(), "indices must be contiguous int32 on GPU");
+  TORCH_CHECK(values.is_cuda() && values.is_contiguous() && values.dim() == 1,
+              "values must be contiguous 1-D on GPU");
+  TORCH_CHECK(values.scalar_type() == torch::kFloat32 ||
+              values.scalar_type() == torch::kFloat64, "values must be float32 or float64");
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 1,
+              "x must be contiguous 1-D on GPU");
+  TORCH_CHECK(x.scalar_type() == values.scalar_type(), "x must have the dtype of values");
+  TORCH_CHECK(indptr.device() == values.device() && indices.device() == values.device() &&
+              x.device() == values.device(), "all operands must be on one device");
+  TORCH_CHECK(n_rows >= 0 && indptr.numel() == n_rows + 1, "indptr must have n_rows + 1 entries");
+  TORCH_CHECK(indices.numel() == values.numel(), "indices and values must have equal length");
+  TORCH_CHECK(n_cols < 0 || x.numel() == n_cols, "x must have n_cols entries");
+  TORCH_CHECK(values.numel() == 0 || x.numel() > 0, "x is empty but the matrix is not");
   auto y = torch::empty({n_rows}, values.options());
   if (values.scalar_type() == torch::kFloat32) {
     raft_amd::launch_csr_spmv<float>(indptr.data_ptr<int>(), indices.data_ptr<int>(),
@@ -1230,7 +1261,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("n"), pybind11::arg("seed"), pybind11::arg("subseq"),
         pybind11::arg("device"), pybind11::arg("gen") = 0);
   m.def("make_blobs", &make_blobs, "fused gaussian blob generator");
-  m.def("csr_spmv", &csr_spmv, "CSR SpMV (sub-wave per row)");
+  m.def("csr_spmv", &csr_spmv, "CSR SpMV (sub-wave per row)",
+        pybind11::arg("indptr"), pybind11::arg("indices"), pybind11::arg("values"),
+        pybind11::arg("x"), pybind11::arg("n_rows"), pybind11::arg("n_cols") = -1);
   m.def("csr_row_stats", &csr_row_stats,
         "per-row statistics of a CSR matrix for a sparse pairwise metric");
   m.def("csr_pairwise", &csr_pairwise,
@@ -1271,11 +1304,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   }, "block_random_sample test driver (weighted in-kernel selection)");
   m.def("sddmm", [](torch::Tensor a, torch::Tensor b, torch::Tensor rows,
                     torch::Tensor cols) {
-    TORCH_CHECK(a.is_cuda() && a.is_contiguous() && b.is_contiguous() &&
+    TORCH_CHECK(a.is_cuda() && b.is_cuda() && rows.is_cuda() && cols.is_cuda() &&
+                b.device() == a.device() && rows.device() == a.device() &&
+                cols.device() == a.device(), "sddmm operands must be on one GPU");
+    TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && a.is_contiguous() && b.is_contiguous() &&
                 a.scalar_type() == torch::kFloat32 &&
+                b.scalar_type() == torch::kFloat32 &&
                 a.size(1) == b.size(1) &&
                 rows.scalar_type() == torch::kInt32 &&
-                cols.scalar_type() == torch::kInt32);
+                cols.scalar_type() == torch::kInt32 &&
+                rows.numel() == cols.numel());
     auto vals = torch::empty({rows.numel()}, a.options());
     raft_amd::launch_sddmm(a.data_ptr<float>(), b.data_ptr<float>(),
                            rows.contiguous().data_ptr<int>(),
@@ -1290,10 +1328,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous() &&
                 x.scalar_type() == torch::kFloat32);
     const long long n = x.size(0), d = x.size(1);
+    TORCH_CHECK(op1 >= 0 && op1 <= 3 && op2 >= 0 && op2 <= 3, "bad linewise op code");
+    // the vectors become raw device pointers: a host or non-fp32 vector must
+    // fail here, not in the kernel
+    TORCH_CHECK(v1.is_cuda() && v1.device() == x.device() &&
+                v1.scalar_type() == torch::kFloat32,
+                "v1 must be float32 on x's device");
     TORCH_CHECK(v1.numel() == (along_rows ? d : n) && v1.is_contiguous());
     const float* v2p = nullptr;
     torch::Tensor v2t;
     if (v2.has_value()) {
+      TORCH_CHECK(v2.value().is_cuda() && v2.value().device() == x.device() &&
+                  v2.value().scalar_type() == torch::kFloat32,
+                  "v2 must be float32 on x's device");
       v2t = v2.value().contiguous();
       TORCH_CHECK(v2t.numel() == v1.numel());
       v2p = v2t.data_ptr<float>();
@@ -1311,6 +1358,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("histogram_f32", [](torch::Tensor x, int64_t n_bins, double lo, double hi) {
     TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous() &&
                 x.scalar_type() == torch::kFloat32);
+    TORCH_CHECK(n_bins >= 1 && n_bins <= 2147483647LL, "n_bins must be in [1, 2^31)");
     auto out = torch::zeros({n_bins, x.size(1)},
                             x.options().dtype(torch::kInt64));
     raft_amd::launch_histogram(
@@ -1323,13 +1371,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bitset_set_", [](torch::Tensor words, torch::Tensor idx, bool value) {
     TORCH_CHECK(words.is_cuda() && words.scalar_type() == torch::kInt32 &&
                 words.is_contiguous() && idx.scalar_type() == torch::kInt64);
+    TORCH_CHECK(idx.is_cuda() && idx.device() == words.device(),
+                "idx must be on the words' device");
     raft_amd::launch_bitset_set(
         reinterpret_cast<unsigned int*>(words.data_ptr<int>()),
         reinterpret_cast<const long long*>(idx.contiguous().data_ptr<int64_t>()),
         idx.numel(), value ? 1 : 0, cur_stream());
   }, "O(k) bitset scatter set/clear");
   m.def("bitset_test", [](torch::Tensor words, torch::Tensor idx) {
-    TORCH_CHECK(words.is_cuda() && words.scalar_type() == torch::kInt32);
+    TORCH_CHECK(words.is_cuda() && words.scalar_type() == torch::kInt32 &&
+                words.is_contiguous());
+    TORCH_CHECK(idx.is_cuda() && idx.device() == words.device() &&
+                idx.scalar_type() == torch::kInt64,
+                "idx must be int64 on the words' device");
     auto out = torch::empty({idx.numel()}, words.options().dtype(torch::kBool));
     raft_amd::launch_bitset_test(
         reinterpret_cast<const unsigned int*>(words.data_ptr<int>()),
@@ -1338,7 +1392,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return out;
   }, "bitset membership test");
   m.def("bitset_count", [](torch::Tensor words) {
-    TORCH_CHECK(words.is_cuda() && words.scalar_type() == torch::kInt32);
+    TORCH_CHECK(words.is_cuda() && words.scalar_type() == torch::kInt32 &&
+                words.is_contiguous());
     auto out = torch::zeros({1}, words.options().dtype(torch::kInt64));
     raft_amd::launch_bitset_count(
         reinterpret_cast<const unsigned int*>(words.data_ptr<int>()),

@@ -111,8 +111,15 @@ struct KahanAcc {
   T c = T(0);
   __device__ __forceinline__ void add(T x) {
     T t = sum + x;
-    if (fabsf((float)sum) >= fabsf((float)x)) c += (sum - t) + x;
-    else c += (x - t) + sum;
+    // a non-finite t (an inf/NaN term, or overflow) has no rounding error to
+    // recover, and (sum - t) + x would be inf - inf = NaN: +/-inf must stay
+    // +/-inf as in a plain sum, so skip the compensation
+    if (isfinite(t)) {
+      // compare in T: a float cast orders doubles beyond the fp32 range wrongly
+      const T as = sum < T(0) ? -sum : sum, ax = x < T(0) ? -x : x;
+      if (as >= ax) c += (sum - t) + x;
+      else c += (x - t) + sum;
+    }
     sum = t;
   }
   __device__ __forceinline__ T get() const { return sum + c; }

@@ -5,22 +5,30 @@
 // nbins (histogram.cuh:52-85).
 //
 // MI355X design (wave64/LDS-first):
-//   * LDS-MULTI  (nbins <= 2048): one LDS sub-histogram PER WAVE
-//     (NW x nbins u32 <= 64 KiB) — wave-private counters kill the LDS atomic
+//   * LDS-MULTI  (nbins <= 4096): one LDS sub-histogram PER WAVE
+//     (NW x nbins u32 <= 64 KiB, NW = 4) — wave-private counters kill the LDS atomic
 //     contention that a single shared histogram has at small nbins (the
 //     reference's smem-bits strategy solves the same contention with packed
 //     counters; wave-privatization is the wave64-native answer).
-//   * LDS-SINGLE (nbins <= 16384): one LDS histogram per block.
+//   * LDS-SINGLE (4096 < nbins <= 16384): one LDS histogram per block.
 //   * GMEM       (larger): device-scope atomics into the output.
 // Grid: (column, row-chunk) — each block bins a row chunk of ONE column and
 // merges into out[bin, col] with one global atomic per touched bin.
-// Binning: linear [lo, hi) -> floor((v - lo) * scale), clamped.
+// Binning: linear [lo, hi) -> floor((v - lo) * scale), clamped; NaN is skipped.
 
 #include <hip/hip_runtime.h>
 
 #include "common.h"
 
 namespace raft_amd {
+
+// floor((v - lo) * scale) clamped to [0, n_bins): the clamp is done in float,
+// so +/-inf and values beyond the int range land in the edge bins without an
+// out-of-range float->int conversion
+__device__ __forceinline__ int hist_bin(float v, float lo, float scale, int n_bins) {
+  const float f = floorf((v - lo) * scale);
+  return f < 0.f ? 0 : (f >= (float)n_bins ? n_bins - 1 : (int)f);
+}
 
 template <int BLOCK, bool MULTI>
 __global__ void histogram_lds_kernel(const float* __restrict__ x, long long n,
@@ -42,8 +50,8 @@ __global__ void histogram_lds_kernel(const float* __restrict__ x, long long n,
   const long long r1 = r0 + rows_per < n ? r0 + rows_per : n;
   for (long long r = r0 + threadIdx.x; r < r1; r += BLOCK) {
     const float v = x[r * d + col];
-    int b = (int)floorf((v - lo) * scale);
-    b = b < 0 ? 0 : (b >= n_bins ? n_bins - 1 : b);
+    if (v != v) continue;  // NaN belongs to no bin
+    const int b = hist_bin(v, lo, scale, n_bins);
     atomicAdd(&mine[b], 1u);
   }
   __syncthreads();
@@ -67,8 +75,8 @@ __global__ void histogram_gmem_kernel(const float* __restrict__ x, long long n,
   const long long r1 = r0 + rows_per < n ? r0 + rows_per : n;
   for (long long r = r0 + threadIdx.x; r < r1; r += BLOCK) {
     const float v = x[r * d + col];
-    int b = (int)floorf((v - lo) * scale);
-    b = b < 0 ? 0 : (b >= n_bins ? n_bins - 1 : b);
+    if (v != v) continue;  // NaN belongs to no bin
+    const int b = hist_bin(v, lo, scale, n_bins);
     atomicAdd(&out[(long long)b * d + col], 1ull);
   }
 }
@@ -76,6 +84,7 @@ __global__ void histogram_gmem_kernel(const float* __restrict__ x, long long n,
 void launch_histogram(const float* x, long long n, long long d, int n_bins,
                       float lo, float hi, unsigned long long* out,
                       hipStream_t stream) {
+  if (d == 0 || n == 0 || n_bins <= 0) return;  // nothing to count; grid x would be 0
   const float scale = (float)n_bins / (hi - lo != 0.f ? hi - lo : 1.f);
   // enough row-chunks to fill 256 CUs x 2 even for few columns
   int nchunks = (int)((512 + d - 1) / d);
@@ -143,6 +152,7 @@ __global__ void bitset_count_kernel(const unsigned int* __restrict__ words,
 
 void launch_bitset_set(unsigned int* words, const long long* idx, long long k,
                        int value, hipStream_t stream) {
+  if (k == 0) return;
   const long long grid = (k + 255) / 256;
   hipLaunchKernelGGL(bitset_set_kernel, dim3((unsigned)grid), dim3(256), 0,
                      stream, words, idx, k, value);
@@ -150,6 +160,7 @@ void launch_bitset_set(unsigned int* words, const long long* idx, long long k,
 
 void launch_bitset_test(const unsigned int* words, const long long* idx,
                         bool* out, long long k, hipStream_t stream) {
+  if (k == 0) return;
   const long long grid = (k + 255) / 256;
   hipLaunchKernelGGL(bitset_test_kernel, dim3((unsigned)grid), dim3(256), 0,
                      stream, words, idx, out, k);
@@ -157,6 +168,7 @@ void launch_bitset_test(const unsigned int* words, const long long* idx,
 
 void launch_bitset_count(const unsigned int* words, long long n_words,
                          unsigned long long* out, hipStream_t stream) {
+  if (n_words == 0) return;  // out is pre-zeroed by the caller
   const long long grid = (n_words + 255) / 256;
   hipLaunchKernelGGL(bitset_count_kernel,
                      dim3((unsigned)(grid < 2048 ? grid : 2048)), dim3(256), 0,

@@ -28,9 +28,21 @@ constexpr bool is_sum() { return OP <= 2; }
 
 template <int OP, typename T>
 __device__ __forceinline__ T red_op(T a, T b) {
+  // min/max propagate NaN from either side (a != a keeps a NaN that arrived
+  // first; a NaN b fails the compare and is taken), so the result does not
+  // depend on where in the row, lane or tile the NaN sits — torch semantics
   if constexpr (OP <= 2) return a + b;
-  else if constexpr (OP == 3 || OP == 5) return a > b ? a : b;
-  else return a < b ? a : b;
+  else if constexpr (OP == 3 || OP == 5) return (a > b || a != a) ? a : b;
+  else return (a < b || a != a) ? a : b;
+}
+
+// argmin order: NaN sorts before every number (torch.argmin returns the first
+// NaN), equal keys break toward the lowest index
+template <typename T>
+__device__ __forceinline__ bool argmin_before(T a, int ai, T b, int bi) {
+  const bool an = a != a, bn = b != b;
+  if (an || bn) return an && (!bn || ai < bi);
+  return a < b || (a == b && ai < bi);
 }
 
 template <int OP, typename T>
@@ -280,14 +292,26 @@ __global__ void row_argmin_kernel(const T* __restrict__ x, int* __restrict__ out
   __shared__ int lds_i[BLOCK / RAFT_AMD_WAVE];
   for (long long row = blockIdx.x; row < n_rows; row += gridDim.x) {
     const T* rp = x + row * d;
+    // (inf, INT_MAX) loses to every real element, an +inf one included
     T v = (T)INFINITY;
-    int vi = 0;
+    int vi = 0x7fffffff;
     for (long long j = threadIdx.x; j < d; j += BLOCK) {
       T t = rp[j];
-      if (t < v || (t == v && (long long)vi > j)) { v = t; vi = (int)j; }
+      if (argmin_before(t, (int)j, v, vi)) { v = t; vi = (int)j; }
     }
-    block_reduce_argmin<T, int, BLOCK>(v, vi, lds_v, lds_i);
-    if (threadIdx.x == 0) out[row] = vi;
+    for (int off = RAFT_AMD_WAVE >> 1; off > 0; off >>= 1) {
+      const T ov = __shfl_xor(v, off, RAFT_AMD_WAVE);
+      const int oi = __shfl_xor(vi, off, RAFT_AMD_WAVE);
+      if (argmin_before(ov, oi, v, vi)) { v = ov; vi = oi; }
+    }
+    const int wid = threadIdx.x / RAFT_AMD_WAVE, lane = threadIdx.x % RAFT_AMD_WAVE;
+    if (lane == 0) { lds_v[wid] = v; lds_i[wid] = vi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int w = 1; w < BLOCK / RAFT_AMD_WAVE; w++)
+        if (argmin_before(lds_v[w], lds_i[w], v, vi)) { v = lds_v[w]; vi = lds_i[w]; }
+      out[row] = vi;
+    }
     __syncthreads();
   }
 }
@@ -330,6 +354,7 @@ __global__ void row_normalize_l2_kernel(const T* __restrict__ x, T* __restrict__
 template <int OP, typename T>
 void launch_reduce_rows(const T* x, T* out, long long n_rows, long long d,
                         hipStream_t stream) {
+  if (n_rows == 0) return;  // no output, and a zero-block grid is a launch error
   if (d <= 256) {
     // thin: logical warp width by D (reference heuristic re-derived for wave64)
     constexpr int BLOCK = 256;
@@ -356,6 +381,7 @@ void launch_reduce_rows(const T* x, T* out, long long n_rows, long long d,
 template <int OP, typename T>
 void launch_reduce_cols(const T* x, T* out, long long n_rows, long long d,
                         hipStream_t stream) {
+  if (d == 0) return;  // no output, and gx would be a zero-block grid
   if (d < 32 && n_rows >= 4096) {
     long long gy = min((long long)1024, (n_rows + 4095) / 4096);
     const long long rows_per_tile = (n_rows + gy - 1) / gy;
@@ -447,6 +473,7 @@ __global__ void rows_sqnorm_bf16_kernel(const __bf16* __restrict__ x,
 
 void launch_rows_sqnorm_bf16(const void* x, float* out, long long n_rows,
                              long long d, hipStream_t stream) {
+  if (n_rows == 0) return;
   long long blocks = n_rows < 65536 ? n_rows : 65536;
   hipLaunchKernelGGL(rows_sqnorm_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0,
                      stream, (const __bf16*)x, out, n_rows, d);
@@ -454,12 +481,14 @@ void launch_rows_sqnorm_bf16(const void* x, float* out, long long n_rows,
 
 void launch_row_argmin(const float* x, int* out, long long n_rows, long long d,
                        hipStream_t stream) {
+  if (n_rows == 0) return;
   int grid = (int)(n_rows < 2048 ? n_rows : 2048);
   hipLaunchKernelGGL((row_argmin_kernel<float>), dim3(grid), dim3(256), 0, stream, x, out, n_rows, d);
 }
 
 void launch_row_normalize_l2(const float* x, float* out, long long n_rows, long long d,
                              float eps, hipStream_t stream) {
+  if (n_rows == 0) return;
   int grid = (int)(n_rows < 2048 ? n_rows : 2048);
   hipLaunchKernelGGL((row_normalize_l2_kernel<float>), dim3(grid), dim3(256), 0, stream, x, out, n_rows, d, eps);
 }

@@ -35,6 +35,7 @@ template <typename T>
 void launch_csr_spmv(const int* indptr, const int* indices, const T* values,
                      const T* x, T* y, long long n_rows, long long nnz,
                      hipStream_t stream) {
+  if (n_rows == 0) return;  // no output, and a zero-block grid is a launch error
   const long long mean = n_rows ? (nnz + n_rows - 1) / n_rows : 1;
   constexpr int BLOCK = 256;
   auto launch = [&](auto swc) {
@@ -93,6 +94,7 @@ __global__ void sddmm_kernel(const float* __restrict__ a,
 void launch_sddmm(const float* a, const float* b, const int* rows,
                   const int* cols, float* vals, long long nnz, long long d,
                   hipStream_t stream) {
+  if (nnz == 0) return;
   constexpr int BLOCK = 256;
   auto launch = [&](auto swc) {
     constexpr int SW = decltype(swc)::value;

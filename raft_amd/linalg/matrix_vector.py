@@ -27,7 +27,8 @@ _OP_CODES = {"add": 0, "sub": 1, "mul": 2, "div": 3}
 def _native_ok(mat, *vecs):
     return (mat.is_cuda and mat.dtype == torch.float32 and mat.dim() == 2
             and mat.is_contiguous()
-            and all(v.dtype == torch.float32 for v in vecs))
+            and all(v.dtype == torch.float32 and v.device == mat.device
+                    for v in vecs))
 
 
 def matrix_vector_op(mat: torch.Tensor, vec: torch.Tensor, op="add",

@@ -28,7 +28,8 @@ def spmv(a, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         ext = require_ext()
         y = ext.csr_spmv(a.indptr.to(torch.int32).contiguous(),
                          a.indices.to(torch.int32).contiguous(),
-                         a.values.contiguous(), x.contiguous(), int(a.n_rows))
+                         a.values.contiguous(), x.contiguous(), int(a.n_rows),
+                         int(a.n_cols))
         if out is not None:
             out.copy_(y)
             return out

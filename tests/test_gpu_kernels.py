@@ -726,7 +726,9 @@ class TestHistogramBitsetGpu:
     @pytest.mark.parametrize("n,d,bins", [(100000, 8, 256), (50000, 3, 4096),
                                           (20000, 2, 20000)])
     def test_histogram_strategies(self, dev, ext, n, d, bins):
-        # each shape hits a different strategy (LDS-multi / LDS / gmem)
+        # 256 and 4096 bins both take LDS-multi (4 waves x 4096 bins x 4 B is
+        # exactly the 64 KiB limit), 20000 bins takes gmem; LDS-single (4097
+        # to 16384 bins) runs in tests/test_gpu_primitives.py
         torch.manual_seed(0)
         x = torch.rand(n, d, device=dev) * 10 - 5
         out = ext.histogram_f32(x.contiguous(), bins, -5.0, 5.0)
