@@ -25,7 +25,7 @@ def run_engine(m, n, d, steps):
     dev = torch.device("cuda")
     x = torch.randn(m, d, device=dev)
     c = torch.randn(n, d, device=dev)
-    from raft_amd.neighbors.fused_l2nn import split_bf16_slices
+    from raft_amd.linalg.split_bf16 import split_bf16_slices
     xs = split_bf16_slices(x, 2)
     cs = split_bf16_slices(c, 2)
     xn = (x * x).sum(dim=1)

@@ -2,7 +2,8 @@
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from raft_amd.neighbors.fused_l2nn import fused_l2nn_presplit, split_bf16_slices
+from raft_amd.linalg.split_bf16 import split_bf16_slices
+from raft_amd.neighbors.fused_l2nn import fused_l2nn_presplit
 
 def run(m=10_000_000, n=1024, d=256, iters=5):
     torch.manual_seed(0)

@@ -45,7 +45,7 @@ def main():
     dev = torch.device("cuda")
     from raft_amd._ext import require_ext
     from raft_amd.neighbors import eps_neighbors_l2sq, eps_neighbors_l2sq_csr
-    from raft_amd.neighbors.fused_l2nn import split_bf16_slices
+    from raft_amd.linalg.split_bf16 import split_bf16_slices
     from raft_amd.random import RngState, make_blobs
     ext = require_ext()
 

@@ -51,7 +51,7 @@ def main():
     assert torch.cuda.is_available(), "this benchmark measures the GPU"
     dev = torch.device("cuda")
     from raft_amd._ext import require_ext
-    from raft_amd.neighbors.fused_l2nn import _MODE_BOUND
+    from raft_amd.linalg.split_bf16 import SPLIT_BOUND
     from raft_amd.random import RngState, make_blobs
     from raft_amd.random.rng import uniform
 
@@ -91,7 +91,7 @@ def main():
         dmin0, amin0, dmin2 = outs[first]
         keys_sorted, perm = torch.sort(amin0)
         perm = perm.to(torch.int32)
-        lead, tail = _MODE_BOUND["bf16x1v"]
+        lead, tail = SPLIT_BOUND[1]
         packed = torch.empty(k * d + k + 1, dtype=torch.float32, device=dev)
         dmin_w, amin_w = dmin0.clone(), amin0.clone()
 

@@ -38,7 +38,8 @@ def main():
     dev = torch.device("cuda")
     from raft_amd.random import make_blobs, RngState
     from raft_amd._ext import require_ext
-    from raft_amd.linalg.gemm import gemm_fp32_emulated, _split_bf16
+    from raft_amd.linalg.gemm import gemm_fp32_emulated
+    from raft_amd.linalg.split_bf16 import split_bf16_slices
 
     ext = require_ext()
     assert args.rows % args.tile_q == 0 and args.rows % args.tile_i == 0, \
@@ -51,7 +52,7 @@ def main():
     out = torch.empty((args.tile_q, args.tile_i), dtype=torch.float32, device=dev)
     if args.mode != "native":
         nsl = 2 if args.mode in ("bf16x2", "mfma2") else 3
-        x_slices = _split_bf16(x, nsl)
+        x_slices = split_bf16_slices(x, nsl)
 
     def tile(q0, q1, i0, i1):
         xq = x[q0:q1]

@@ -593,27 +593,60 @@ std::tuple<std::string, int64_t> l2nn_resolve_engine(int64_t nslice, int64_t m,
   return {raft_amd::l2nn_engine_name(plan.engine), plan.gt};
 }
 
+// the split-bf16 operands of one call: checked slice lists and their shape
+struct SliceArgs {
+  const void* xsl[3];
+  const void* csl[3];
+  int nslice;
+  long long m, n, d;
+};
+
+// 1 to max_nslice bf16 slices per side, equal counts; every slice a contiguous
+// 2-D GPU tensor with the sizes of slice 0 of its list; x and y of equal d, a
+// multiple of 64 (the launchers index every slice with these sizes)
+static SliceArgs checked_slices(const char* who, const std::vector<torch::Tensor>& x_slices,
+                                const std::vector<torch::Tensor>& y_slices,
+                                int max_nslice) {
+  SliceArgs a;
+  a.nslice = (int)x_slices.size();
+  TORCH_CHECK(a.nslice >= 1 && a.nslice <= max_nslice && y_slices.size() == x_slices.size(),
+              who, ": x and y need the same number of slices, 1 to ", max_nslice);
+  for (int s = 0; s < a.nslice; s++) {
+    for (const auto* list : {&x_slices, &y_slices}) {
+      const auto& t = (*list)[s];
+      TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kBFloat16 && t.dim() == 2 &&
+                  t.is_contiguous() && t.sizes() == (*list)[0].sizes(),
+                  who, ": every slice must be a contiguous bf16 [rows, d] GPU tensor "
+                  "with the sizes of slice 0");
+    }
+    a.xsl[s] = x_slices[s].data_ptr();
+    a.csl[s] = y_slices[s].data_ptr();
+  }
+  a.m = x_slices[0].size(0);
+  a.n = y_slices[0].size(0);
+  a.d = x_slices[0].size(1);
+  TORCH_CHECK(y_slices[0].size(1) == a.d, who, ": x and y slices must have the same d");
+  TORCH_CHECK(a.d % 64 == 0, who, ": d must be a multiple of 64");
+  return a;
+}
+
+// row norms and their like: a contiguous fp32 GPU tensor of numel elements
+static const float* checked_f32_vec(const char* who, const char* what,
+                                    const torch::Tensor& t, long long numel) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.is_contiguous() &&
+              t.numel() == numel, who, ": ", what,
+              " must be a contiguous fp32 GPU tensor of ", numel, " elements");
+  return t.data_ptr<float>();
+}
+
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> fused_l2nn_split(
     std::vector<torch::Tensor> x_slices, std::vector<torch::Tensor> c_slices,
     torch::Tensor xn, torch::Tensor cn, const std::string& engine, int64_t gt) {
-  const int nslice = (int)x_slices.size();
-  TORCH_CHECK(nslice >= 1 && nslice <= 3 && c_slices.size() == x_slices.size());
-  const void* xsl[3];
-  const void* csl[3];
-  for (int s = 0; s < nslice; s++) {
-    auto& xt = x_slices[s];
-    auto& ct = c_slices[s];
-    TORCH_CHECK(xt.is_cuda() && xt.scalar_type() == torch::kBFloat16 && xt.is_contiguous());
-    TORCH_CHECK(ct.is_cuda() && ct.scalar_type() == torch::kBFloat16 && ct.is_contiguous());
-    xsl[s] = xt.data_ptr();
-    csl[s] = ct.data_ptr();
-  }
-  const long long m = x_slices[0].size(0);
-  const long long n = c_slices[0].size(0);
-  const long long d = x_slices[0].size(1);
-  TORCH_CHECK(c_slices[0].size(1) == d, "dim mismatch");
-  const auto plan = l2nn_plan(nslice, m, n, d, engine, gt);
-  TORCH_CHECK(cn.numel() == n && xn.numel() == m);
+  SliceArgs a = checked_slices("fused_l2nn_split", x_slices, c_slices, 3);
+  const long long m = a.m, n = a.n, d = a.d;
+  const auto plan = l2nn_plan(a.nslice, m, n, d, engine, gt);
+  const float* xnp = checked_f32_vec("fused_l2nn_split", "xn", xn, m);
+  const float* cnp = checked_f32_vec("fused_l2nn_split", "cn", cn, n);
   auto dmin = torch::empty({m}, xn.options());
   auto amin = torch::empty({m}, xn.options().dtype(torch::kInt32));
   auto dmin2 = torch::empty({m}, xn.options());
@@ -621,11 +654,10 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> fused_l2nn_split(
   auto pd = torch::empty({plan.n_groups * m}, xn.options());
   auto pd2 = torch::empty({plan.n_groups * m}, xn.options());
   auto pi = torch::empty({plan.n_groups * m}, xn.options().dtype(torch::kInt32));
-  raft_amd::launch_fused_l2nn(plan, xsl, csl, xn.data_ptr<float>(),
-                              cn.data_ptr<float>(), pd.data_ptr<float>(),
+  raft_amd::launch_fused_l2nn(plan, a.xsl, a.csl, xnp, cnp, pd.data_ptr<float>(),
                               pd2.data_ptr<float>(), pi.data_ptr<int>(),
                               dmin.data_ptr<float>(), amin.data_ptr<int>(),
-                              dmin2.data_ptr<float>(), m, (int)n, (int)d, nslice,
+                              dmin2.data_ptr<float>(), m, (int)n, (int)d, a.nslice,
                               cur_stream());
   return {dmin, amin, dmin2};
 }
@@ -633,33 +665,21 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> fused_l2nn_split(
 // one pairwise L2 call: checked bf16 slices, shape, and the kernel `variant`
 // resolves to ("auto" -> environment and defaults; an unknown name or a named
 // variant that cannot run the shape is an error, never a fallback)
-struct PwCall {
-  const void* xsl[3];
-  const void* csl[3];
-  int nslice;
-  long long m, n, d;
+struct PwCall : SliceArgs {
+  const float* xn;
+  const float* yn;
   raft_amd::PwPlan plan;
 };
 
 static PwCall pw_call(raft_amd::PwFamily family, const char* who,
                       const std::vector<torch::Tensor>& x_slices,
                       const std::vector<torch::Tensor>& y_slices,
+                      const torch::Tensor& xn, const torch::Tensor& yn,
                       const std::string& variant) {
   PwCall c;
-  c.nslice = (int)x_slices.size();
-  TORCH_CHECK(c.nslice >= 1 && c.nslice <= 3 && y_slices.size() == x_slices.size());
-  for (int s = 0; s < c.nslice; s++) {
-    TORCH_CHECK(x_slices[s].is_cuda() && x_slices[s].scalar_type() == torch::kBFloat16
-                && x_slices[s].is_contiguous());
-    TORCH_CHECK(y_slices[s].is_cuda() && y_slices[s].scalar_type() == torch::kBFloat16
-                && y_slices[s].is_contiguous());
-    c.xsl[s] = x_slices[s].data_ptr();
-    c.csl[s] = y_slices[s].data_ptr();
-  }
-  c.m = x_slices[0].size(0);
-  c.n = y_slices[0].size(0);
-  c.d = x_slices[0].size(1);
-  TORCH_CHECK(c.d % 64 == 0, who, ": d must be a multiple of 64");
+  static_cast<SliceArgs&>(c) = checked_slices(who, x_slices, y_slices, 3);
+  c.xn = checked_f32_vec(who, "xn", xn, c.m);
+  c.yn = checked_f32_vec(who, "yn", yn, c.n);
   bool known;
   const auto v = raft_amd::pw_variant_from_name(family, variant, &known);
   TORCH_CHECK(known, who, ": unknown variant '", variant, "'");
@@ -675,7 +695,7 @@ torch::Tensor pairwise_l2_mfma(std::vector<torch::Tensor> x_slices,
                                c10::optional<torch::Tensor> out, bool sqrt_out,
                                const std::string& variant) {
   PwCall c = pw_call(raft_amd::PwFamily::Tile, "pairwise_l2_mfma", x_slices,
-                           y_slices, variant);
+                     y_slices, xn, yn, variant);
   torch::Tensor o;
   if (out.has_value()) {
     o = out.value();
@@ -683,8 +703,8 @@ torch::Tensor pairwise_l2_mfma(std::vector<torch::Tensor> x_slices,
   } else {
     o = torch::empty({c.m, c.n}, xn.options());
   }
-  raft_amd::launch_pairwise_l2_tile(c.plan, c.xsl, c.csl, xn.data_ptr<float>(),
-                                    yn.data_ptr<float>(), o.data_ptr<float>(), c.m, c.n,
+  raft_amd::launch_pairwise_l2_tile(c.plan, c.xsl, c.csl, c.xn, c.yn,
+                                    o.data_ptr<float>(), c.m, c.n,
                                     (int)c.d, o.size(1), c.nslice, sqrt_out,
                                     cur_stream());
   return o;
@@ -710,12 +730,12 @@ void pairwise_l2_filter(std::vector<torch::Tensor> x_slices,
                         torch::Tensor out_i, torch::Tensor cnt, int64_t col_offset,
                         const std::string& variant) {
   PwCall c = pw_call(raft_amd::PwFamily::Filter, "pairwise_l2_filter", x_slices,
-                           y_slices, variant);
+                     y_slices, xn, yn, variant);
   const int cap = (int)out_d.size(1);
   TORCH_CHECK(out_d.size(0) == c.m && out_i.sizes() == out_d.sizes());
   TORCH_CHECK(cnt.scalar_type() == torch::kInt32 && cnt.numel() == c.m);
-  raft_amd::launch_pairwise_l2_filter(c.plan, c.xsl, c.csl, xn.data_ptr<float>(),
-                                      yn.data_ptr<float>(), thr.data_ptr<float>(),
+  raft_amd::launch_pairwise_l2_filter(c.plan, c.xsl, c.csl, c.xn, c.yn,
+                                      thr.data_ptr<float>(),
                                       out_d.data_ptr<float>(), out_i.data_ptr<int>(),
                                       cnt.data_ptr<int>(), cap, col_offset, c.m, c.n,
                                       (int)c.d, c.nslice, cur_stream());
@@ -736,32 +756,13 @@ void eps_neighbors_l2sq(std::vector<torch::Tensor> x_slices,
                         c10::optional<torch::Tensor> yf, torch::Tensor bitmap,
                         c10::optional<torch::Tensor> rechecked, int64_t n_cols,
                         double eps_sq, double lead, double tail) {
-  const int nslice = (int)x_slices.size();
-  TORCH_CHECK(nslice >= 1 && nslice <= 2 && y_slices.size() == x_slices.size(),
-              "eps_neighbors_l2sq: 1 or 2 slices");
-  const void* xsl[3];
-  const void* csl[3];
-  for (int s = 0; s < nslice; s++) {
-    TORCH_CHECK(x_slices[s].is_cuda() && x_slices[s].scalar_type() == torch::kBFloat16
-                && x_slices[s].is_contiguous() && x_slices[s].dim() == 2);
-    TORCH_CHECK(y_slices[s].is_cuda() && y_slices[s].scalar_type() == torch::kBFloat16
-                && y_slices[s].is_contiguous() && y_slices[s].dim() == 2);
-    TORCH_CHECK(x_slices[s].sizes() == x_slices[0].sizes() &&
-                y_slices[s].sizes() == y_slices[0].sizes());
-    xsl[s] = x_slices[s].data_ptr();
-    csl[s] = y_slices[s].data_ptr();
-  }
-  const long long m = x_slices[0].size(0);
-  const long long n = y_slices[0].size(0);
-  const long long d = x_slices[0].size(1);
+  SliceArgs a = checked_slices("eps_neighbors_l2sq", x_slices, y_slices, 2);
+  const int nslice = a.nslice;
+  const long long m = a.m, n = a.n, d = a.d;
   TORCH_CHECK(n == n_cols, "eps_neighbors_l2sq: y slices must have n_cols rows");
-  TORCH_CHECK(d % 64 == 0 && y_slices[0].size(1) == d,
-              "eps_neighbors_l2sq: d must be a multiple of 64 and equal for x and y");
   TORCH_CHECK(n < (1ll << 31) && m < (1ll << 31), "eps_neighbors_l2sq: m, n < 2^31");
-  TORCH_CHECK(xn.is_cuda() && xn.scalar_type() == torch::kFloat32 && xn.is_contiguous()
-              && xn.numel() == m);
-  TORCH_CHECK(yn.is_cuda() && yn.scalar_type() == torch::kFloat32 && yn.is_contiguous()
-              && yn.numel() == n);
+  const float* xnp = checked_f32_vec("eps_neighbors_l2sq", "xn", xn, m);
+  const float* ynp = checked_f32_vec("eps_neighbors_l2sq", "yn", yn, n);
   const float eps2 = (float)eps_sq;
   TORCH_CHECK(eps2 >= 0.f && eps2 <= std::numeric_limits<float>::max(),
               "eps_neighbors_l2sq: eps_sq must be finite and >= 0");
@@ -793,8 +794,7 @@ void eps_neighbors_l2sq(std::vector<torch::Tensor> x_slices,
   } else {
     TORCH_CHECK(nslice == 1, "eps_neighbors_l2sq: 2 slices need the fp32 recheck");
   }
-  raft_amd::launch_eps_neighbors_l2sq(xsl, csl, xn.data_ptr<float>(),
-                                      yn.data_ptr<float>(), xfp, yfp, bm, cnt, eps2,
+  raft_amd::launch_eps_neighbors_l2sq(a.xsl, a.csl, xnp, ynp, xfp, yfp, bm, cnt, eps2,
                                       (float)lead, (float)tail, m, n, (int)d, (int)df,
                                       n_words, nslice, cur_stream());
 }
@@ -832,32 +832,13 @@ std::vector<torch::Tensor> masked_l2nn(std::vector<torch::Tensor> x_slices,
                                        c10::optional<torch::Tensor> adj,
                                        c10::optional<torch::Tensor> x_group,
                                        torch::Tensor scratch, torch::Tensor counters) {
-  const int nslice = (int)x_slices.size();
-  TORCH_CHECK(nslice >= 1 && nslice <= 2 && y_slices.size() == x_slices.size(),
-              "masked_l2nn: 1 or 2 slices");
-  const void* xsl[3];
-  const void* csl[3];
-  for (int s = 0; s < nslice; s++) {
-    TORCH_CHECK(x_slices[s].is_cuda() && x_slices[s].scalar_type() == torch::kBFloat16
-                && x_slices[s].is_contiguous() && x_slices[s].dim() == 2);
-    TORCH_CHECK(y_slices[s].is_cuda() && y_slices[s].scalar_type() == torch::kBFloat16
-                && y_slices[s].is_contiguous() && y_slices[s].dim() == 2);
-    TORCH_CHECK(x_slices[s].sizes() == x_slices[0].sizes() &&
-                y_slices[s].sizes() == y_slices[0].sizes());
-    xsl[s] = x_slices[s].data_ptr();
-    csl[s] = y_slices[s].data_ptr();
-  }
-  const long long m = x_slices[0].size(0);
-  const long long n = y_slices[0].size(0);
-  const long long d = x_slices[0].size(1);
+  SliceArgs a = checked_slices("masked_l2nn", x_slices, y_slices, 2);
+  const long long m = a.m, n = a.n, d = a.d;
   TORCH_CHECK(m >= 1 && n >= 1, "masked_l2nn: empty inputs are handled by the caller");
-  TORCH_CHECK(d % 64 == 0 && d > 0 && y_slices[0].size(1) == d,
-              "masked_l2nn: d must be a multiple of 64 and equal for x and y");
+  TORCH_CHECK(d > 0, "masked_l2nn: d must be positive");
   TORCH_CHECK(n < (1ll << 31) - 128 && m < (1ll << 31), "masked_l2nn: m, n < 2^31");
-  TORCH_CHECK(xn.is_cuda() && xn.scalar_type() == torch::kFloat32 && xn.is_contiguous()
-              && xn.numel() == m);
-  TORCH_CHECK(yn.is_cuda() && yn.scalar_type() == torch::kFloat32 && yn.is_contiguous()
-              && yn.numel() == n);
+  const float* xnp = checked_f32_vec("masked_l2nn", "xn", xn, m);
+  const float* ynp = checked_f32_vec("masked_l2nn", "yn", yn, n);
   TORCH_CHECK(n_groups >= 1 && n_groups < (1ll << 31), "masked_l2nn: n_groups >= 1");
   const int* yg = masked_nn_i32(y_group, n, "y_group");
   const int* xg = masked_nn_i32(x_group, m, "x_group");
@@ -881,10 +862,10 @@ std::vector<torch::Tensor> masked_l2nn(std::vector<torch::Tensor> x_slices,
   auto dmin2 = torch::empty({(int64_t)m}, xn.options());
   auto amin = torch::empty({(int64_t)m}, xn.options().dtype(torch::kInt32));
   raft_amd::launch_masked_l2nn(
-      xsl, csl, xn.data_ptr<float>(), yn.data_ptr<float>(), yg, ap, adj_words, xg, pd,
+      a.xsl, a.csl, xnp, ynp, yg, ap, adj_words, xg, pd,
       pd2, pi, dmin.data_ptr<float>(), amin.data_ptr<int>(), dmin2.data_ptr<float>(),
       reinterpret_cast<unsigned long long*>(counters.data_ptr<int64_t>()), m, (int)n,
-      (int)d, (int)n_split, nslice, cur_stream());
+      (int)d, (int)n_split, a.nslice, cur_stream());
   return {dmin, amin, dmin2};
 }
 

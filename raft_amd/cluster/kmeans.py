@@ -254,15 +254,14 @@ def kmeans_fit(x: torch.Tensor, params: KMeansParams,
         centroids = _init_plusplus(x, k, state, comms, params.fp32_mode,
                                    sample_weights=sample_weights)
 
-    from raft_amd.neighbors.fused_l2nn import (_MODE_NSLICE, _VERIFY_MODES,
-                                               fused_l2nn_presplit,
-                                               split_bf16_slices)
+    from raft_amd.linalg.split_bf16 import VERIFY_MODES, split_bf16_slices
+    from raft_amd.neighbors.fused_l2nn import FUSED_NSLICE, fused_l2nn_presplit
     use_fused = (x.is_cuda and x.dtype == torch.float32
-                 and params.fp32_mode in _MODE_NSLICE and d % 64 == 0)
+                 and params.fp32_mode in FUSED_NSLICE and d % 64 == 0)
     if use_fused:
-        x_slices = split_bf16_slices(x, _MODE_NSLICE[params.fp32_mode])
+        x_slices = split_bf16_slices(x, FUSED_NSLICE[params.fp32_mode])
         xn = (x * x).sum(dim=1)
-        vx = x if params.fp32_mode in _VERIFY_MODES else None
+        vx = x if params.fp32_mode in VERIFY_MODES else None
 
     inertia = float("inf")
     it = 0
@@ -331,20 +330,25 @@ def kmeans_fit(x: torch.Tensor, params: KMeansParams,
     return KMeansModel(centroids=centroids, inertia=inertia, n_iter=it, labels=labels)
 
 
+#: slices "auto" starts on: the adaptive loop runs the 1-product engine first
+#: and widens to the mode's 2 slices if too many rows would rescan
+_AUTO_START_NSLICE = 1
+
+
 def kmeans_iter_state(x: torch.Tensor, fp32_mode: str = "auto"):
     """Precompute the iteration-invariant inputs (bf16 slices of X + row
     norms) ONCE per fit — reusable across kmeans_iterate calls. On GPU this
     is a single fused kernel pass (ext.split_bf16_norms)."""
-    from raft_amd.neighbors.fused_l2nn import _MODE_NSLICE, split_bf16_slices
+    from raft_amd.neighbors.fused_l2nn import FUSED_NSLICE
     from raft_amd._ext import require_ext
 
-    if not (x.is_cuda and x.dtype == torch.float32 and fp32_mode in _MODE_NSLICE
+    if not (x.is_cuda and x.dtype == torch.float32 and fp32_mode in FUSED_NSLICE
             and x.shape[1] % 64 == 0):
         return None
     # "auto" starts on the 1-product engine: materialize only slice 0 here
     # (halves the split memory and the one-time split pass); the adaptive
     # loop appends the residual slice lazily if it widens to 2-slice
-    nslice = 1 if fp32_mode == "auto" else _MODE_NSLICE[fp32_mode]
+    nslice = _AUTO_START_NSLICE if fp32_mode == "auto" else FUSED_NSLICE[fp32_mode]
     ext = require_ext()
     slices = [torch.empty_like(x, dtype=torch.bfloat16) for _ in range(nslice)]
     xn = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
@@ -361,37 +365,35 @@ def kmeans_iterate(x: torch.Tensor, centroids: torch.Tensor, n_iters: int,
     (fused L2-NN over all rows) + update (keyed reduction, counts, ONE packed
     allreduce, centroid recompute). Returns (centroids, inertia).
     """
-    from raft_amd.neighbors.fused_l2nn import (_DEFAULT_BOUND, _MODE_BOUND,
-                                               _MODE_NSLICE, _VERIFY_MODES,
-                                               fused_l2nn_presplit,
-                                               split_bf16_slices)
+    from raft_amd.linalg.split_bf16 import (SPLIT_BOUND, VERIFY_MODES,
+                                            pad_features)
+    from raft_amd.neighbors.fused_l2nn import FUSED_NSLICE, fused_l2nn_presplit
 
     comms = comms or LoopbackComms()
     k, d = centroids.shape
     inertia = float("inf")
-    bound = _MODE_BOUND.get(fp32_mode, _DEFAULT_BOUND)
-    if (x.is_cuda and x.dtype == torch.float32 and fp32_mode in _MODE_NSLICE
+    if (x.is_cuda and x.dtype == torch.float32 and fp32_mode in FUSED_NSLICE
             and d % 64 != 0):
         # zero feature columns change nothing (distances, sums, counts all
         # identical; padded centroid columns stay 0): pad to the MFMA K
         # granularity so ANY d takes the fused engines
-        dp = (-d) % 64
-        xp = torch.nn.functional.pad(x, (0, dp))
-        cp = torch.nn.functional.pad(centroids, (0, dp))
-        c_out, inertia = kmeans_iterate(xp, cp, n_iters, comms=comms,
+        c_out, inertia = kmeans_iterate(pad_features(x), pad_features(centroids),
+                                        n_iters, comms=comms,
                                         fp32_mode=fp32_mode,
                                         chunk_rows=chunk_rows)
         return c_out[:, :d].contiguous(), inertia
     # X is iteration-invariant: pre-split the bf16 slices and row norms ONCE
     # (the same caching the reference does for row norms in its kmeans)
     use_fused = (x.is_cuda and x.dtype == torch.float32
-                 and fp32_mode in _MODE_NSLICE and d % 64 == 0)
+                 and fp32_mode in FUSED_NSLICE and d % 64 == 0)
     if use_fused:
         if state is None:
             state = kmeans_iter_state(x, fp32_mode)
         x_slices, xn = state
     if use_fused:
-        if fp32_mode != "auto" and len(x_slices) < _MODE_NSLICE[fp32_mode]:
+        # the envelope of the mode's slice count (read by verified modes only)
+        bound = SPLIT_BOUND[FUSED_NSLICE[fp32_mode]]
+        if fp32_mode != "auto" and len(x_slices) < FUSED_NSLICE[fp32_mode]:
             # a 1-slice "auto" state reused with an explicit 2-slice mode:
             # materialize the residual slice (the adaptive path does this
             # lazily itself)
@@ -401,11 +403,11 @@ def kmeans_iterate(x: torch.Tensor, centroids: torch.Tensor, n_iters: int,
                                            [x_slices[0], s_new], xn)
             x_slices.append(s_new)
         return _fast_iterate(x, x_slices, xn, centroids.contiguous().clone(),
-                             n_iters, comms, _MODE_NSLICE[fp32_mode],
-                             fp32_mode in _VERIFY_MODES, bound,
+                             n_iters, comms, FUSED_NSLICE[fp32_mode],
+                             fp32_mode in VERIFY_MODES, bound,
                              adaptive=(fp32_mode == "auto"))
 
-    if use_fused and len(x_slices) < _MODE_NSLICE[fp32_mode]:
+    if use_fused and len(x_slices) < FUSED_NSLICE[fp32_mode]:
         # the generic loop below has no adaptive widen: materialize the
         # full split upfront ("auto" state carries only slice 0 initially)
         from raft_amd._ext import require_ext
@@ -416,7 +418,7 @@ def kmeans_iterate(x: torch.Tensor, centroids: torch.Tensor, n_iters: int,
     inertia_t = None
     for it in range(n_iters):
         if use_fused:
-            vx = x if fp32_mode in _VERIFY_MODES else None
+            vx = x if fp32_mode in VERIFY_MODES else None
             dmin, labels = fused_l2nn_presplit(x_slices, xn, centroids,
                                                int32_labels=True, verify_x=vx,
                                                bound=bound)
@@ -473,7 +475,7 @@ def _fast_iterate(x, x_slices, xn, centroids, n_iters, comms, nslice, verify,
     """
     import os
     from raft_amd._ext import require_ext
-    from raft_amd.neighbors.fused_l2nn import _MODE_BOUND
+    from raft_amd.linalg.split_bf16 import SPLIT_BOUND
     ext = require_ext()
     k, d = centroids.shape
     dev = x.device
@@ -489,7 +491,7 @@ def _fast_iterate(x, x_slices, xn, centroids, n_iters, comms, nslice, verify,
                                            device=dev)])
     kp = k + pad
     cur_nslice = 1 if (adaptive and verify) else nslice
-    cur_bound = _MODE_BOUND["bf16x1v"] if (adaptive and verify) else bound
+    cur_bound = SPLIT_BOUND[cur_nslice] if (adaptive and verify) else bound
     frac_t = [None]  # first-iteration provable-rescan fraction (device)
     c_slices = [torch.empty((kp, d), dtype=torch.bfloat16, device=dev)
                 for _ in range(nslice)]

@@ -28,6 +28,8 @@ import torch
 from raft_amd._ext import require_ext
 from raft_amd.utils import on_gpu
 from raft_amd.linalg.gemm import gemm_fp32_emulated
+from raft_amd.linalg.split_bf16 import (MODE_NSLICE, pad_features,
+                                        split_bf16_slices)
 
 
 class DistanceType(Enum):
@@ -169,9 +171,7 @@ def _l2_squared(x, y, fp32_mode):
                      and fp32_mode in ("bf16x2", "bf16x3", "mfma")))):
         # zero feature columns change no L2 distance: pad to the MFMA K
         # granularity so any d rides the single-write tile kernel
-        dp = (-x.shape[1]) % 64
-        return _l2_squared(torch.nn.functional.pad(x, (0, dp)),
-                           torch.nn.functional.pad(y, (0, dp)), fp32_mode)
+        return _l2_squared(pad_features(x), pad_features(y), fp32_mode)
     if on_gpu(x, y) and x.dtype == torch.bfloat16:
         ext = require_ext()
         xn = x.float().pow(2).sum(dim=1)
@@ -185,9 +185,8 @@ def _l2_squared(x, y, fp32_mode):
     if (on_gpu(x, y) and x.dtype == torch.float32 and x.shape[1] % 64 == 0
             and fp32_mode in ("bf16x2", "bf16x3", "mfma")):
         # split-bf16 MFMA tile kernel: distance tile written exactly once
-        from raft_amd.neighbors.fused_l2nn import split_bf16_slices
         ext = require_ext()
-        nsl = 2 if fp32_mode == "bf16x2" else 3
+        nsl = MODE_NSLICE[fp32_mode]
         xs = split_bf16_slices(x, nsl)
         ys = split_bf16_slices(y, nsl)
         xn = (x * x).sum(dim=1)

@@ -22,6 +22,7 @@ import torch
 
 from raft_amd._ext import require_ext
 from raft_amd.utils import on_gpu
+from raft_amd.linalg.split_bf16 import split_bf16_slices
 
 
 def gemm(a: torch.Tensor, b: torch.Tensor, alpha: float = 1.0, beta: float = 0.0,
@@ -74,15 +75,8 @@ def axpy(alpha: float, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
 # fp32 emulation on bf16 MFMA
 # ---------------------------------------------------------------------------
 
-def _split_bf16(a: torch.Tensor, n: int):
-    """Split fp32 tensor into n bf16 slices with a ≈ sum(slices)."""
-    slices = []
-    resid = a
-    for _ in range(n):
-        s = resid.to(torch.bfloat16)
-        slices.append(s)
-        resid = resid - s.to(torch.float32)
-    return slices
+#: the name the benchmarks import
+_split_bf16 = split_bf16_slices
 
 
 def gemm_bf16_f32(a_bf16: torch.Tensor, b_bf16: torch.Tensor,
@@ -115,13 +109,13 @@ def gemm_fp32_emulated(a: torch.Tensor, b: torch.Tensor, mode: str = "bf16x3") -
     assert a.dtype == torch.float32 and b.dtype == torch.float32
     fused = on_gpu(a, b)  # rocBLAS beta=1 accumulates in-GEMM (no extra passes)
     if mode == "bf16x2":
-        ah, al = _split_bf16(a, 2)
-        bh, bl = _split_bf16(b, 2)
+        ah, al = split_bf16_slices(a, 2)
+        bh, bl = split_bf16_slices(b, 2)
         c = gemm_bf16_f32(ah, bh)
         terms = [(ah, bl), (al, bh)]
     elif mode == "bf16x3":
-        ah, am, al = _split_bf16(a, 3)
-        bh, bm, bl = _split_bf16(b, 3)
+        ah, am, al = split_bf16_slices(a, 3)
+        bh, bm, bl = split_bf16_slices(b, 3)
         c = gemm_bf16_f32(ah, bh)
         terms = [(ah, bm), (am, bh), (am, bm), (ah, bl), (al, bh)]
     elif mode == "native":

@@ -29,6 +29,8 @@ import torch
 
 from raft_amd._ext import require_ext
 from raft_amd.distance import pairwise_distance, DistanceType
+from raft_amd.linalg.split_bf16 import (MODE_NSLICE, SPLIT_BOUND, pad_features,
+                                        row_sqnorms, split_bf16_slices)
 from raft_amd.matrix.select_k import select_k
 from raft_amd.utils import row_chunks
 
@@ -61,13 +63,10 @@ def knn(x: torch.Tensor, queries: torch.Tensor, k: int,
                   and x.shape[0] >= 8 * k
                   and x.dtype in (torch.bfloat16, torch.float32)
                   and not (x.dtype == torch.float32 and fp32_mode == "native"))
-    if filterable and x.shape[1] % 64 != 0:
+    if filterable:
         # zero feature columns change no distance: pad to the MFMA K
         # granularity and keep the filtered path (round-1 d-cliff)
-        dp = (-x.shape[1]) % 64
-        x = torch.nn.functional.pad(x, (0, dp))
-        queries = torch.nn.functional.pad(queries, (0, dp))
-    if filterable:
+        x, queries = pad_features(x), pad_features(queries)
         return _knn_gpu_filtered(x, queries, k, fp32_mode, res=res)
     return _knn_tiled(x, queries, k, metric, query_chunk, index_chunk, fp32_mode)
 
@@ -88,14 +87,14 @@ class BruteForceIndex:
         self._filterable = (
             x.is_cuda and x.dtype in (torch.bfloat16, torch.float32)
             and not (x.dtype == torch.float32 and fp32_mode == "native"))
-        if self._filterable and x.shape[1] % 64 != 0:
+        if self._filterable:
             # pad the MFMA K granularity ONCE at build (zero columns change
             # no distance); search pads queries to match
-            x = torch.nn.functional.pad(x, (0, (-x.shape[1]) % 64))
+            x = pad_features(x)
         self.x = x
         if self._filterable:
             self.slices = _slices_of(x, fp32_mode)
-            self.xn = _norms(x)
+            self.xn = row_sqnorms(x)
         else:
             self.slices = None
             self.xn = None
@@ -143,35 +142,22 @@ def _tiles_from_budget(budget_bytes: int, q: int, n: int, d: int, k: int):
     return int(q_chunk), int(index_chunk)
 
 
+#: the filter's "auto": 1 slice (1/3 MFMA work, half the slice stream) — the
+#: wider 2^-7 inflation admits a provable candidate superset and the exact
+#: re-rank + margin proof keeps results exact-fp32 either way (measured
+#: 30M x 128 randn: 61.1k vs 27.5k q/s, idx agreement 0.9999 with dist diffs
+#: at fp32 rounding)
+_AUTO_MODE = "bf16x1v"
+
+
 def _slices_of(t: torch.Tensor, fp32_mode: str):
-    from raft_amd.neighbors.fused_l2nn import split_bf16_slices
     if t.dtype == torch.bfloat16:
         return [t.contiguous()]
-    # auto: the 1-slice filter (1/3 MFMA work, half the slice stream) — the
-    # wider 2^-7 inflation admits a provable candidate superset and the
-    # exact re-rank + margin proof keeps results exact-fp32 either way
-    # (measured 30M x 128 randn: 61.1k vs 27.5k q/s, idx agreement 0.9999
-    # with dist diffs at fp32 rounding). Explicit "bf16x2"/"bf16x3" keep
-    # the tighter filters for near-tie-heavy corpora.
-    nsl = {"bf16x3": 3, "bf16x1v": 1, "auto": 1}.get(fp32_mode, 2)
+    # only "bf16x1v" and "bf16x3" pick their own width; every other name
+    # ("bf16x2", "bf16x2v", "mfma", "fused", ...) keeps the 2-slice filter
+    mode = _AUTO_MODE if fp32_mode == "auto" else fp32_mode
+    nsl = MODE_NSLICE[mode] if mode in ("bf16x1v", "bf16x3") else 2
     return split_bf16_slices(t, nsl)
-
-
-#: provable |Δdot| <= lead*sqrt(qn*xn) + tail*(qn+xn) envelopes per slice
-#: count (same family as the verified L2NN engine, csrc/kmeans.hip)
-_KNN_BOUND = {1: (2.0 ** -7, 2.0 ** -12),
-              2: (2.0 ** -13, 2.0 ** -18),
-              3: (2.0 ** -21, 2.0 ** -24)}
-
-
-def _norms(t: torch.Tensor) -> torch.Tensor:
-    if t.is_cuda and t.dtype == torch.bfloat16:
-        # native kernel: a torch float() chain would materialize a 2x-size
-        # fp32 copy (51 GB for the 100M-row index — allocation-bound)
-        return require_ext().rows_sqnorm_bf16(t.contiguous())
-    if t.is_cuda and t.dtype == torch.float32:
-        return require_ext().reduce_rows(t.contiguous(), 1)
-    return t.float().pow(2).sum(dim=1).contiguous()
 
 
 def _knn_gpu_filtered(x, queries, k, fp32_mode, index_chunk: int = 4_000_000,
@@ -209,9 +195,9 @@ def _knn_gpu_filtered_block(x, queries, k, fp32_mode, index_chunk, res,
     dev = queries.device
 
     q_slices = _slices_of(queries, fp32_mode)
-    qn = _norms(queries)
+    qn = row_sqnorms(queries)
     pre_slices = pre[0] if pre is not None else None
-    xn_full = pre[1] if pre is not None else _norms(x)
+    xn_full = pre[1] if pre is not None else row_sqnorms(x)
 
     # ---- 1. sample -> per-row thresholds -----------------------------------
     s = max(min(65536, n), n // 1024)
@@ -245,7 +231,7 @@ def _knn_gpu_filtered_block(x, queries, k, fp32_mode, index_chunk, res,
     emulated = queries.dtype != torch.bfloat16
     if emulated:
         xm = float(xn_full.max())
-        lead, tail = _KNN_BOUND[nslice]
+        lead, tail = SPLIT_BOUND[nslice]
         thr = thr + 4.0 * (lead * torch.sqrt(qn.clamp_min(0) * xm)
                            + tail * (qn + xm))
 

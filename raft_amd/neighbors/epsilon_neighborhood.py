@@ -31,12 +31,13 @@ import torch
 
 from raft_amd._ext import require_ext
 from raft_amd.utils import row_chunks
+from raft_amd.linalg.split_bf16 import (MODE_NSLICE, SPLIT_BOUND, pad_features,
+                                        row_sqnorms, split_bf16_slices)
 
 _FP32_MODES = ("auto", "bf16x1v", "bf16x2v", "native")
 #: the verified engine "auto" resolves to (see docs/performance.md,
 #: "Eps-neighborhood", for the measurement behind the choice)
 _AUTO_MODE = "bf16x2v"
-_NSLICE = {"bf16x1v": 1, "bf16x2v": 2}
 
 _BIT_VALUES = [1 << k for k in range(31)] + [-(1 << 31)]
 
@@ -145,29 +146,23 @@ def _native_filler(x, y, eps):
 def _mfma_filler(x, y, eps, mode, self_join, counter):
     """The MFMA bitmap engine. fp32: verified (band pairs rechecked in exact
     fp32, counted into `counter`); bf16: one slice, exact in its own dtype."""
-    from raft_amd.neighbors.brute_force import _KNN_BOUND, _norms
-    from raft_amd.neighbors.fused_l2nn import split_bf16_slices
     ext = require_ext()
     x = x.contiguous()
     y = x if self_join else y.contiguous()
     n = y.shape[0]
-    dp = (-x.shape[1]) % 64
-
-    def pad(t):
-        # zero feature columns change no distance
-        return torch.nn.functional.pad(t, (0, dp)) if dp else t
-
+    # the slices carry zero-padded features (no distance changes); the norms
+    # and the exact recheck read the rows as given
     if x.dtype == torch.bfloat16:
         nsl, xf, yf, cnt = 1, None, None, None
-        xs = [pad(x).contiguous()]
-        ys = xs if self_join else [pad(y).contiguous()]
+        xs = [pad_features(x).contiguous()]
+        ys = xs if self_join else [pad_features(y).contiguous()]
     else:
-        nsl, xf, yf, cnt = _NSLICE[mode], x, y, counter
-        xs = split_bf16_slices(pad(x), nsl)
-        ys = xs if self_join else split_bf16_slices(pad(y), nsl)
-    lead, tail = _KNN_BOUND[nsl]
-    xn = _norms(x)
-    yn = xn if self_join else _norms(y)
+        nsl, xf, yf, cnt = MODE_NSLICE[mode], x, y, counter
+        xs = split_bf16_slices(pad_features(x), nsl)
+        ys = xs if self_join else split_bf16_slices(pad_features(y), nsl)
+    lead, tail = SPLIT_BOUND[nsl]
+    xn = row_sqnorms(x)
+    yn = xn if self_join else row_sqnorms(y)
 
     def fill(s0, s1, bm):
         ext.eps_neighbors_l2sq([t[s0:s1] for t in xs], ys, xn[s0:s1], yn,

@@ -22,34 +22,16 @@ import torch
 from raft_amd._ext import ext_or_none, require_ext
 from raft_amd.utils import on_gpu, row_chunks
 from raft_amd.linalg.gemm import gemm_fp32_emulated
+from raft_amd.linalg.split_bf16 import (MODE_NSLICE, SPLIT_BOUND, VERIFY_MODES,
+                                        pad_features, split_bf16_slices)
 
-_MODE_NSLICE = {"bf16x2": 2, "bf16x3": 3, "bf16x2v": 2, "bf16x1v": 1,
-                "auto": 2, "fused": 3}
-#: modes that run the exact-fp32 verification/repair pass (provably exact
-#: argmin: rows inside the split-error margin are rescanned in fp32, and the
-#: chosen distance is recomputed exactly for every row)
-_VERIFY_MODES = {"bf16x2v", "bf16x1v", "auto"}
-#: (lead, tail) margin-bound constants per verified mode — the provable
-#: |Δdot| <= lead*sqrt(xn*cn) + tail*(xn+cn) envelope of the split emulation
-#: (derivation: csrc/kmeans.hip l2nn_verify_repair_kernel). bf16x1v does a
-#: single MFMA product (1/3 the matrix work of bf16x2v) against a 2^6-wider
-#: bound; correctness is identical — only the rescan fraction grows on data
-#: with near-tied neighbors.
-_MODE_BOUND = {"bf16x1v": (2.0 ** -7, 2.0 ** -12)}
-_DEFAULT_BOUND = (2.0 ** -13, 2.0 ** -18)
-
-
-def split_bf16_slices(t: torch.Tensor, nslice: int):
-    """fp32 -> bf16 slices with t ≈ sum(slices). Iteration-invariant for the
-    k-means X matrix, so callers may precompute (see kmeans_iterate)."""
-    slices = []
-    resid = t
-    for i in range(nslice):
-        s = resid.to(torch.bfloat16)
-        slices.append(s.contiguous())
-        if i + 1 < nslice:
-            resid = resid - s.to(torch.float32)
-    return slices
+#: the engine "auto" resolves to: 2 slices, verified
+_AUTO_MODE = "bf16x2v"
+#: slices per fp32 mode the fused kernel serves ("mfma" is a pairwise-only
+#: name: here it takes the GEMM + epilogue path like any other unlisted mode)
+FUSED_NSLICE = {m: MODE_NSLICE[_AUTO_MODE if m == "auto" else m]
+                for m in ("auto", "bf16x1v", "bf16x2", "bf16x2v", "bf16x3",
+                          "fused")}
 
 
 def _pad_cols(y: torch.Tensor, yn: torch.Tensor, mult: int = 128):
@@ -65,7 +47,7 @@ def _pad_cols(y: torch.Tensor, yn: torch.Tensor, mult: int = 128):
 def fused_l2nn_presplit(x_slices, xn: torch.Tensor, y: torch.Tensor,
                         sqrt: bool = False, int32_labels: bool = False,
                         verify_x: torch.Tensor | None = None,
-                        bound: tuple[float, float] = _DEFAULT_BOUND):
+                        bound: tuple[float, float] | None = None):
     """Fused kernel entry with precomputed X slices (k-means hot loop).
 
     verify_x: the original fp32 matrix — enables the exact-fp32
@@ -73,10 +55,13 @@ def fused_l2nn_presplit(x_slices, xn: torch.Tensor, y: torch.Tensor,
     chosen distance is recomputed in exact fp32, and rows whose
     (best, second-best) margin falls inside the provable split-emulation error
     bound rescan all centroids exactly. Result: fp32-exact argmin + fp32
-    distances at split-bf16 MFMA speed.
+    distances at split-bf16 MFMA speed. bound: the (lead, tail) envelope of
+    that pass; defaults to the one of the slice count, SPLIT_BOUND[nslice].
     """
     ext = require_ext()
     nslice = len(x_slices)
+    if bound is None:
+        bound = SPLIT_BOUND[nslice]
     yn = (y * y).sum(dim=1)
     yp, ynp, n_true = _pad_cols(y, yn)
     y_slices = split_bf16_slices(yp, nslice)
@@ -110,15 +95,12 @@ def fused_l2nn(x: torch.Tensor, y: torch.Tensor, sqrt: bool = False,
                                     chunk_rows=chunk_rows)
             return dmin, amin
         if (d % 64 != 0 and x.dtype in (torch.float32, torch.bfloat16)
-                and (x.dtype == torch.bfloat16 or fp32_mode in _MODE_NSLICE)):
+                and (x.dtype == torch.bfloat16 or fp32_mode in FUSED_NSLICE)):
             # zero columns leave every pairwise distance unchanged: pad to
             # the MFMA K granularity and take the fused path (closes the
             # round-1 "d % 64 falls back to chunked GEMM" perf cliff)
-            dp = (-d) % 64
-            xp = torch.nn.functional.pad(x, (0, dp))
-            yp = torch.nn.functional.pad(y, (0, dp))
-            return fused_l2nn(xp, yp, sqrt=sqrt, fp32_mode=fp32_mode,
-                              chunk_rows=chunk_rows)
+            return fused_l2nn(pad_features(x), pad_features(y), sqrt=sqrt,
+                              fp32_mode=fp32_mode, chunk_rows=chunk_rows)
         if x.dtype == torch.bfloat16 and d % 64 == 0:
             ext = require_ext()
             xn = x.to(torch.float32).pow(2).sum(dim=1)
@@ -131,14 +113,11 @@ def fused_l2nn(x: torch.Tensor, y: torch.Tensor, sqrt: bool = False,
                 dmin = dmin.clamp_min(0).sqrt()
             return dmin, amin.to(torch.int64)
         if x.dtype == torch.float32:
-            if fp32_mode in _MODE_NSLICE and d % 64 == 0:
-                nslice = _MODE_NSLICE[fp32_mode]
-                xs = split_bf16_slices(x, nslice)
+            if fp32_mode in FUSED_NSLICE and d % 64 == 0:
+                xs = split_bf16_slices(x, FUSED_NSLICE[fp32_mode])
                 xn = (x * x).sum(dim=1)
-                vx = x if fp32_mode in _VERIFY_MODES else None
-                return fused_l2nn_presplit(
-                    xs, xn, y, sqrt=sqrt, verify_x=vx,
-                    bound=_MODE_BOUND.get(fp32_mode, _DEFAULT_BOUND))
+                vx = x if fp32_mode in VERIFY_MODES else None
+                return fused_l2nn_presplit(xs, xn, y, sqrt=sqrt, verify_x=vx)
             return _chunked_gpu(x, y, sqrt, fp32_mode, chunk_rows)
 
     # CPU oracle

@@ -27,13 +27,12 @@ import torch
 from raft_amd._ext import require_ext
 from raft_amd.utils import row_chunks
 from raft_amd.neighbors.epsilon_neighborhood import _pack_rows, _unpack_rows
-from raft_amd.neighbors.fused_l2nn import (_DEFAULT_BOUND, _MODE_BOUND,
-                                           split_bf16_slices)
+from raft_amd.linalg.split_bf16 import (MODE_NSLICE, SPLIT_BOUND, pad_features,
+                                        row_sqnorms, split_bf16_slices)
 
 _FP32_MODES = ("auto", "bf16x1v", "bf16x2v", "native")
 #: the verified engine "auto" resolves to (docs/performance.md, "Masked L2-NN")
 _AUTO_MODE = "bf16x2v"
-_NSLICE = {"bf16x1v": 1, "bf16x2v": 2}
 #: blocks one launch aims for (2 resident blocks on each of 256 CUs, twice
 #: over) and the most column splits a row tile is cut into
 _TARGET_BLOCKS = 1024
@@ -136,26 +135,22 @@ def _dense_path(x, y, yg, adj_bool, xg, y_rank, native):
 def _mfma_path(x, y, yg, ends, adj, packed, xg, y_rank, mode, res):
     """The masked MFMA tile engine + (fp32) the exact verify / repair pass."""
     from raft_amd.core.resources import get_resources
-    from raft_amd.neighbors.brute_force import _norms
     ext = require_ext()
     dev = x.device
     x, y = x.contiguous(), y.contiguous()
     m, n, d = x.shape[0], y.shape[0], x.shape[1]
     n_groups = ends.numel()
-    dp = (-d) % 64
-
-    def pad(t):
-        # zero feature columns change no distance
-        return torch.nn.functional.pad(t, (0, dp)) if dp else t
-
+    # the slices carry zero-padded features (no distance changes); the norms
+    # and the exact verify pass read the rows as given
     verify = x.dtype != torch.bfloat16
     if verify:
-        nsl = _NSLICE[mode]
-        xs, ys = split_bf16_slices(pad(x), nsl), split_bf16_slices(pad(y), nsl)
-        lead, tail = _MODE_BOUND.get(mode, _DEFAULT_BOUND)
+        nsl = MODE_NSLICE[mode]
+        xs = split_bf16_slices(pad_features(x), nsl)
+        ys = split_bf16_slices(pad_features(y), nsl)
+        lead, tail = SPLIT_BOUND[nsl]
     else:
-        xs, ys = [pad(x).contiguous()], [pad(y).contiguous()]
-    xn, yn = _norms(x), _norms(y)
+        xs, ys = [pad_features(x).contiguous()], [pad_features(y).contiguous()]
+    xn, yn = row_sqnorms(x), row_sqnorms(y)
     yg32 = yg.to(torch.int32)
     adj_w = None
     if adj is not None:

@@ -179,15 +179,15 @@ class TestRound2Surface:
     def test_adaptive_engine_surface(self):
         """Late-round-2 surfaces: the bf16x1v verified mode, its bound
         constants, and the kNN per-slice inflation table."""
-        from raft_amd.neighbors.fused_l2nn import (_DEFAULT_BOUND, _MODE_BOUND,
-                                                   _MODE_NSLICE, _VERIFY_MODES)
-        assert _MODE_NSLICE["bf16x1v"] == 1 and "bf16x1v" in _VERIFY_MODES
-        lead, tail = _MODE_BOUND["bf16x1v"]
+        from raft_amd.linalg.split_bf16 import (MODE_NSLICE, SPLIT_BOUND,
+                                                VERIFY_MODES)
+        assert MODE_NSLICE["bf16x1v"] == 1 and "bf16x1v" in VERIFY_MODES
+        lead, tail = SPLIT_BOUND[MODE_NSLICE["bf16x1v"]]
         # the 1-slice bound is exactly 2^6 wider than the 2-slice bound
-        assert lead == _DEFAULT_BOUND[0] * 64 and tail == _DEFAULT_BOUND[1] * 64
-        from raft_amd.neighbors.brute_force import _KNN_BOUND, _slices_of
-        assert set(_KNN_BOUND) == {1, 2, 3}
-        assert _KNN_BOUND[1] == (lead, tail)
+        assert lead == SPLIT_BOUND[2][0] * 64 and tail == SPLIT_BOUND[2][1] * 64
+        from raft_amd.neighbors.brute_force import _slices_of
+        assert set(SPLIT_BOUND) == {1, 2, 3}
+        assert SPLIT_BOUND[1] == (2.0 ** -7, 2.0 ** -12)
         x = torch.randn(8, 64)
         assert len(_slices_of(x, "auto")) == 1          # 1-slice auto filter
         assert len(_slices_of(x, "bf16x2")) == 2

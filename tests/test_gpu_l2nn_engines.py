@@ -54,7 +54,7 @@ def _case(m, n, d):
 
 
 def _slices(t, nslice):
-    from raft_amd.neighbors.fused_l2nn import split_bf16_slices
+    from raft_amd.linalg.split_bf16 import split_bf16_slices
     return [t.to(torch.bfloat16)] if nslice == 1 else split_bf16_slices(t, nslice)
 
 
