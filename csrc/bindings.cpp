@@ -451,6 +451,10 @@ void kmeans_update_verify(torch::Tensor x, torch::Tensor perm,
                           double lead, double tail) {
   check_f32_2d(x, "x");
   check_f32_2d(c, "c");
+  // the widest kernel instance holds 16 columns per lane: past 64 * 16 the
+  // remaining columns would be dropped from sums, distances and rescans
+  TORCH_CHECK(x.size(1) <= 1024, "kmeans_update_verify: d = ", x.size(1),
+              " exceeds the 1024 columns the kernel covers");
   TORCH_CHECK(perm.scalar_type() == torch::kInt32 && keys_sorted.scalar_type() == torch::kInt32);
   TORCH_CHECK(sums.is_contiguous() && counts.is_contiguous());
   raft_amd::launch_kmeans_update_verify(

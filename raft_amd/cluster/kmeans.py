@@ -7,24 +7,34 @@ config 3: fit 10M x 256 fp32, k=1024, 8 MI355X over RCCL/xGMI.
 MI355X design:
   * assignment step = fused L2-NN (distance tile + argmin, registers only;
     split-bf16 MFMA for the dot-product term on fp32 data),
-  * update step = reduce_rows_by_key (LDS-binned atomics) + bincount,
+  * update step = keyed row sums over the label-sorted rows (register
+    accumulation per key run, atomics only at run boundaries) with the counts
+    and the inertia folded into the same pass; the verified engines also
+    refine every chosen distance in exact fp32 there,
   * distributed: rows are sharded across ranks (one process per GPU); per-iter
     global state is ONE allreduce of the [k, d+2] packed (sums | counts |
-    inertia) buffer — a few MB over xGMI, negligible vs compute, and overlapped
-    with nothing because the EM dependency is serial (SURVEY §6 notes the
-    collective is tiny vs the distance phase).
+    inertia) buffer — a few MB over xGMI. Large shards split their rows in
+    two halves so one half's allreduce hides under the other's compute.
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+import functools
+import math
+import os
+from dataclasses import dataclass, replace
 
 import torch
 
+from raft_amd._ext import require_ext
 from raft_amd.comms import Comms, LoopbackComms, ReduceOp
-from raft_amd.linalg.reduce_by_key import reduce_rows_by_key
-from raft_amd.neighbors.fused_l2nn import fused_l2nn
-from raft_amd.random.rng import RngState, sample_without_replacement, uniform
 from raft_amd.distance import pairwise_distance
+from raft_amd.linalg.reduce_by_key import reduce_rows_by_key
+from raft_amd.linalg.split_bf16 import (SPLIT_BOUND, VERIFY_MODES, pad_features,
+                                        split_bf16_slices)
+from raft_amd.matrix.sample_rows import sample_rows
+from raft_amd.neighbors.fused_l2nn import (FUSED_NSLICE, fused_l2nn,
+                                           fused_l2nn_presplit)
+from raft_amd.random.rng import RngState, sample_without_replacement, uniform
 
 
 @dataclass
@@ -79,7 +89,6 @@ def _init_plusplus(x: torch.Tensor, k: int, state: RngState, comms: Comms,
     rank/row proportionally and broadcast; candidate potentials are computed
     from one [n_local, L] GEMM-shaped distance block and allreduced.
     """
-    import math
     n_local, d = x.shape
     world = comms.get_size()
     rank = comms.get_rank()
@@ -110,49 +119,47 @@ def _init_plusplus(x: torch.Tensor, k: int, state: RngState, comms: Comms,
             us = uniform((n_trials,), state=state, device=x.device).double() * total
             js = torch.searchsorted(cdf, us.to(cdf.dtype)).clamp_(max=n_local - 1)
             cmat = x[js]                                       # [L, d]
-            d2 = (xsq.unsqueeze(1) + (cmat * cmat).sum(dim=1)
-                  - 2.0 * (x @ cmat.T)).clamp_min_(0).double()
-            pot = torch.minimum(mind2.unsqueeze(1), d2)
-            pot = (pot if w is None else pot * w.unsqueeze(1)).sum(dim=0)
-            best = int(pot.argmin().item())
-            centers.append(cmat[best])
-            mind2 = torch.minimum(mind2, d2[:, best])
-            continue
-        cands = []
-        for t in range(n_trials):
-            u = float(uniform((1,), state=state, device=x.device).item()) * total
-            # pick owning rank by prefix sums
-            csum = 0.0
-            owner, local_u = 0, u
-            for r in range(world):
-                s = float(sums[r].item())
-                if u < csum + s or r == world - 1:
-                    owner, local_u = r, u - csum
-                    break
-                csum += s
-            if rank == owner:
-                j = int(torch.searchsorted(cdf, torch.tensor(local_u, dtype=cdf.dtype,
-                                                             device=cdf.device)).item())
-                j = min(j, n_local - 1)
-                cand = x[j:j + 1].clone()
-            else:
-                cand = torch.empty((1, d), dtype=x.dtype, device=x.device)
-            if world > 1:
-                cand = comms.bcast(cand, root=owner)
-            cands.append(cand[0])
-        cmat = torch.stack(cands, dim=0)                       # [L, d]
-        # [n_local, L] squared distances in fp32 (no fp64 copy of x):
-        # ||x||^2 + ||c||^2 - 2 x.c — selection only needs ~1e-7 relative
-        d2 = (xsq.unsqueeze(1) + (cmat * cmat).sum(dim=1)
-              - 2.0 * (x @ cmat.T)).clamp_min_(0).double()
-        pot = torch.minimum(mind2.unsqueeze(1), d2)             # [n_local, L]
-        pot = (pot if w is None else pot * w.unsqueeze(1)).sum(dim=0)  # [L]
-        if world > 1:
-            comms.allreduce(pot, op=ReduceOp.SUM)
-        best = int(pot.argmin().item())
-        centers.append(cmat[best])
-        mind2 = torch.minimum(mind2, d2[:, best])
+        else:
+            cands = []
+            for t in range(n_trials):
+                u = float(uniform((1,), state=state, device=x.device).item()) * total
+                # pick owning rank by prefix sums
+                csum = 0.0
+                owner, local_u = 0, u
+                for r in range(world):
+                    s = float(sums[r].item())
+                    if u < csum + s or r == world - 1:
+                        owner, local_u = r, u - csum
+                        break
+                    csum += s
+                if rank == owner:
+                    j = int(torch.searchsorted(cdf, torch.tensor(local_u, dtype=cdf.dtype,
+                                                                 device=cdf.device)).item())
+                    j = min(j, n_local - 1)
+                    cand = x[j:j + 1].clone()
+                else:
+                    cand = torch.empty((1, d), dtype=x.dtype, device=x.device)
+                cands.append(comms.bcast(cand, root=owner)[0])
+            cmat = torch.stack(cands, dim=0)                   # [L, d]
+        center, mind2 = _keep_best_candidate(x, xsq, cmat, mind2, w, comms)
+        centers.append(center)
     return torch.stack(centers, dim=0)
+
+
+def _keep_best_candidate(x, xsq, cmat, mind2, w, comms):
+    """One greedy k-means++ selection: of the candidate rows cmat [L, d], keep
+    the one that minimizes the (weighted, global) potential. Returns it with
+    the min-sq-distances updated for it."""
+    # [n_local, L] squared distances in fp32 (no fp64 copy of x):
+    # ||x||^2 + ||c||^2 - 2 x.c — selection only needs ~1e-7 relative
+    d2 = (xsq.unsqueeze(1) + (cmat * cmat).sum(dim=1)
+          - 2.0 * (x @ cmat.T)).clamp_min_(0).double()
+    pot = torch.minimum(mind2.unsqueeze(1), d2)                 # [n_local, L]
+    pot = (pot if w is None else pot * w.unsqueeze(1)).sum(dim=0)  # [L]
+    if comms.get_size() > 1:
+        comms.allreduce(pot, op=ReduceOp.SUM)
+    best = int(pot.argmin().item())
+    return cmat[best], torch.minimum(mind2, d2[:, best])
 
 
 def _init_scalable(x: torch.Tensor, k: int, state: RngState, comms: Comms,
@@ -231,7 +238,6 @@ def kmeans_fit(x: torch.Tensor, params: KMeansParams,
     deterministically so every rank replays the same trials.
     """
     if params.n_init > 1 and init_centroids is None and params.init != "array":
-        from dataclasses import replace
         best = None
         for trial in range(params.n_init):
             p = replace(params, n_init=1, seed=params.seed + 9973 * trial)
@@ -241,7 +247,7 @@ def kmeans_fit(x: torch.Tensor, params: KMeansParams,
         return best
     comms = comms or LoopbackComms()
     state = RngState(seed=params.seed)
-    k, (n_local, d) = params.n_clusters, x.shape
+    k, d = params.n_clusters, x.shape[1]
 
     if init_centroids is not None or params.init == "array":
         centroids = init_centroids.to(x.device, x.dtype).clone()
@@ -254,52 +260,26 @@ def kmeans_fit(x: torch.Tensor, params: KMeansParams,
         centroids = _init_plusplus(x, k, state, comms, params.fp32_mode,
                                    sample_weights=sample_weights)
 
-    from raft_amd.linalg.split_bf16 import VERIFY_MODES, split_bf16_slices
-    from raft_amd.neighbors.fused_l2nn import FUSED_NSLICE, fused_l2nn_presplit
-    use_fused = (x.is_cuda and x.dtype == torch.float32
-                 and params.fp32_mode in FUSED_NSLICE and d % 64 == 0)
-    if use_fused:
-        x_slices = split_bf16_slices(x, FUSED_NSLICE[params.fp32_mode])
+    nslice = _fused_nslice(x, params.fp32_mode, d)
+    if nslice is not None:
+        # X is iteration-invariant: split it once, not once per assignment
+        x_slices = split_bf16_slices(x, nslice)
         xn = (x * x).sum(dim=1)
         vx = x if params.fp32_mode in VERIFY_MODES else None
+        assign = functools.partial(fused_l2nn_presplit, x_slices, xn, verify_x=vx)
+    else:
+        assign = functools.partial(fused_l2nn, x, fp32_mode=params.fp32_mode)
 
     inertia = float("inf")
     it = 0
     labels = None
     for it in range(1, params.max_iter + 1):
-        if use_fused:
-            dmin, labels = fused_l2nn_presplit(x_slices, xn, centroids, verify_x=vx)
-        else:
-            dmin, labels = fused_l2nn(x, centroids, fp32_mode=params.fp32_mode)
-        # accumulate sums/counts/inertia in fp32 regardless of x.dtype —
-        # bf16 cannot represent counts > 256 exactly, so half-precision
-        # accumulation silently corrupts centroids of large clusters
-        acc = torch.float32 if x.dtype in (torch.bfloat16, torch.float16) \
-            else x.dtype
-        if sample_weights is None:
-            sums = reduce_rows_by_key(x, labels, n_keys=k, out_dtype=acc)
-            counts = torch.bincount(labels, minlength=k).to(acc)
-            local_inertia = torch.sum(dmin, dtype=torch.float64).to(acc)
-        else:
-            w = sample_weights.to(acc)
-            sums = reduce_rows_by_key(x, labels, n_keys=k, weights=w, out_dtype=acc)
-            counts = torch.zeros(k, dtype=acc, device=x.device)
-            counts.index_add_(0, labels.to(torch.int64), w)
-            local_inertia = torch.sum(dmin.to(acc) * w, dtype=torch.float64).to(acc)
-        # ONE packed allreduce: [k, d] sums | [k] counts | [1] inertia
-        packed = torch.cat([sums.reshape(-1), counts, local_inertia.reshape(1)])
-        if comms.get_size() > 1:
-            comms.allreduce(packed, op=ReduceOp.SUM)
-        sums = packed[: k * d].reshape(k, d)
-        counts = packed[k * d: k * d + k]
-        inertia = float(packed[-1].item())
-        nonzero = counts > 0
-        new_centroids = centroids.clone()
-        new_centroids[nonzero] = (sums[nonzero]
-                                  / counts[nonzero].unsqueeze(1)).to(x.dtype)
+        new_centroids, counts, inertia_t, dmin, labels = _lloyd_step(
+            x, centroids, assign, comms, sample_weights)
+        inertia = float(inertia_t.item())
         # empty clusters: relocate to the globally farthest point (reference
         # relocates empties; here: owner rank = argmax of local max-dmin)
-        empties = (~nonzero).nonzero(as_tuple=True)[0]
+        empties = (~(counts > 0)).nonzero(as_tuple=True)[0]
         if empties.numel():
             used = set()
             order = torch.argsort(dmin, descending=True)
@@ -330,30 +310,93 @@ def kmeans_fit(x: torch.Tensor, params: KMeansParams,
     return KMeansModel(centroids=centroids, inertia=inertia, n_iter=it, labels=labels)
 
 
+def _accum_dtype(dtype: torch.dtype) -> torch.dtype:
+    """Sums, counts and inertia of half-precision data accumulate in fp32: bf16
+    holds no count > 256 exactly, which corrupts the centroids of large clusters."""
+    return torch.float32 if dtype in (torch.bfloat16, torch.float16) else dtype
+
+
+def _lloyd_step(x, centroids, assign, comms, sample_weights=None):
+    """One generic Lloyd step on this rank's shard. assign(centroids) gives
+    (dmin, labels); sums by key, counts and the inertia then travel in ONE
+    packed allreduce. Returns (new centroids, counts, inertia, dmin, labels);
+    the inertia stays a device scalar, so the caller decides when to sync."""
+    k, d = centroids.shape
+    dmin, labels = assign(centroids)
+    acc = _accum_dtype(x.dtype)
+    if sample_weights is None:
+        sums = reduce_rows_by_key(x, labels, n_keys=k, out_dtype=acc)
+        counts = torch.bincount(labels, minlength=k).to(acc)
+        local_inertia = torch.sum(dmin, dtype=torch.float64).to(acc)
+    else:
+        w = sample_weights.to(acc)
+        sums = reduce_rows_by_key(x, labels, n_keys=k, weights=w, out_dtype=acc)
+        counts = torch.zeros(k, dtype=acc, device=x.device)
+        counts.index_add_(0, labels.to(torch.int64), w)
+        local_inertia = torch.sum(dmin.to(acc) * w, dtype=torch.float64).to(acc)
+    # [k, d] sums | [k] counts | [1] inertia
+    packed = torch.cat([sums.reshape(-1), counts, local_inertia.reshape(1)])
+    if comms.get_size() > 1:
+        comms.allreduce(packed, op=ReduceOp.SUM)
+    sums = packed[: k * d].reshape(k, d)
+    counts = packed[k * d: k * d + k]
+    # sums / counts where a cluster has members, the old centroid elsewhere
+    # (no boolean indexing: that would sync the host every step)
+    nonzero = counts > 0
+    mean = sums / torch.where(nonzero, counts, torch.ones_like(counts)).unsqueeze(1)
+    new_centroids = torch.where(nonzero.unsqueeze(1), mean.to(x.dtype), centroids)
+    return new_centroids, counts, packed[-1], dmin, labels
+
+
 #: slices "auto" starts on: the adaptive loop runs the 1-product engine first
 #: and widens to the mode's 2 slices if too many rows would rescan
 _AUTO_START_NSLICE = 1
+#: columns the widest kmeans_update_verify kernel instance covers (16 per lane)
+_UPDATE_VERIFY_MAX_D = 1024
+
+
+def _fused_nslice(x: torch.Tensor, fp32_mode: str, d: int):
+    """Slices of the mode if fp32 data of (padded) width d takes the fused
+    route (presplit X; in kmeans_iterate the minimal-dispatch loop), else None.
+    A verified mode wider than its update kernel covers takes the generic loop,
+    whose verify/repair and keyed reduction are written for any d."""
+    fused = (x.is_cuda and x.dtype == torch.float32 and fp32_mode in FUSED_NSLICE
+             and d % 64 == 0
+             and not (fp32_mode in VERIFY_MODES and d > _UPDATE_VERIFY_MAX_D))
+    return FUSED_NSLICE[fp32_mode] if fused else None
+
+
+class KMeansIterState:
+    """Iteration-invariant operands of one X shard: bf16 slices and row norms.
+    Made by kmeans_iter_state and passed to kmeans_iterate as state=; slices
+    that one call adds stay for the next."""
+
+    def __init__(self, x: torch.Tensor, nslice: int):
+        self.x = x.contiguous()
+        self.slices = []
+        self.xn = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+        self.ensure(nslice)
+
+    def ensure(self, nslice: int) -> None:
+        """Make sure nslice slices exist. One fused pass writes all of them
+        and xn; slices that existed already get identical values again."""
+        if len(self.slices) < nslice:
+            self.slices += [torch.empty_like(self.x, dtype=torch.bfloat16)
+                            for _ in range(nslice - len(self.slices))]
+            require_ext().split_bf16_norms(self.x, self.slices, self.xn)
 
 
 def kmeans_iter_state(x: torch.Tensor, fp32_mode: str = "auto"):
     """Precompute the iteration-invariant inputs (bf16 slices of X + row
     norms) ONCE per fit — reusable across kmeans_iterate calls. On GPU this
-    is a single fused kernel pass (ext.split_bf16_norms)."""
-    from raft_amd.neighbors.fused_l2nn import FUSED_NSLICE
-    from raft_amd._ext import require_ext
-
-    if not (x.is_cuda and x.dtype == torch.float32 and fp32_mode in FUSED_NSLICE
-            and x.shape[1] % 64 == 0):
+    is a single fused kernel pass (ext.split_bf16_norms). None where
+    kmeans_iterate takes the generic loop."""
+    nslice = _fused_nslice(x, fp32_mode, x.shape[1])
+    if nslice is None:
         return None
-    # "auto" starts on the 1-product engine: materialize only slice 0 here
-    # (halves the split memory and the one-time split pass); the adaptive
-    # loop appends the residual slice lazily if it widens to 2-slice
-    nslice = _AUTO_START_NSLICE if fp32_mode == "auto" else FUSED_NSLICE[fp32_mode]
-    ext = require_ext()
-    slices = [torch.empty_like(x, dtype=torch.bfloat16) for _ in range(nslice)]
-    xn = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
-    ext.split_bf16_norms(x.contiguous(), slices, xn)
-    return slices, xn
+    # "auto" starts on the 1-product engine: only slice 0 here (half the split
+    # memory and pass); the adaptive loop adds the residual slice if it widens
+    return KMeansIterState(x, _AUTO_START_NSLICE if fp32_mode == "auto" else nslice)
 
 
 def kmeans_iterate(x: torch.Tensor, centroids: torch.Tensor, n_iters: int,
@@ -365,98 +408,43 @@ def kmeans_iterate(x: torch.Tensor, centroids: torch.Tensor, n_iters: int,
     (fused L2-NN over all rows) + update (keyed reduction, counts, ONE packed
     allreduce, centroid recompute). Returns (centroids, inertia).
     """
-    from raft_amd.linalg.split_bf16 import (SPLIT_BOUND, VERIFY_MODES,
-                                            pad_features)
-    from raft_amd.neighbors.fused_l2nn import FUSED_NSLICE, fused_l2nn_presplit
-
     comms = comms or LoopbackComms()
-    k, d = centroids.shape
-    inertia = float("inf")
-    if (x.is_cuda and x.dtype == torch.float32 and fp32_mode in FUSED_NSLICE
-            and d % 64 != 0):
+    d = centroids.shape[1]
+    if d % 64 and _fused_nslice(x, fp32_mode, d + (-d) % 64) is not None:
         # zero feature columns change nothing (distances, sums, counts all
         # identical; padded centroid columns stay 0): pad to the MFMA K
         # granularity so ANY d takes the fused engines
         c_out, inertia = kmeans_iterate(pad_features(x), pad_features(centroids),
-                                        n_iters, comms=comms,
-                                        fp32_mode=fp32_mode,
+                                        n_iters, comms=comms, fp32_mode=fp32_mode,
                                         chunk_rows=chunk_rows)
         return c_out[:, :d].contiguous(), inertia
-    # X is iteration-invariant: pre-split the bf16 slices and row norms ONCE
-    # (the same caching the reference does for row norms in its kmeans)
-    use_fused = (x.is_cuda and x.dtype == torch.float32
-                 and fp32_mode in FUSED_NSLICE and d % 64 == 0)
-    if use_fused:
-        if state is None:
-            state = kmeans_iter_state(x, fp32_mode)
-        x_slices, xn = state
-    if use_fused:
-        # the envelope of the mode's slice count (read by verified modes only)
-        bound = SPLIT_BOUND[FUSED_NSLICE[fp32_mode]]
-        if fp32_mode != "auto" and len(x_slices) < FUSED_NSLICE[fp32_mode]:
-            # a 1-slice "auto" state reused with an explicit 2-slice mode:
-            # materialize the residual slice (the adaptive path does this
-            # lazily itself)
-            from raft_amd._ext import require_ext
-            s_new = torch.empty_like(x_slices[0])
-            require_ext().split_bf16_norms(x.contiguous(),
-                                           [x_slices[0], s_new], xn)
-            x_slices.append(s_new)
-        return _fast_iterate(x, x_slices, xn, centroids.contiguous().clone(),
-                             n_iters, comms, FUSED_NSLICE[fp32_mode],
-                             fp32_mode in VERIFY_MODES, bound,
-                             adaptive=(fp32_mode == "auto"))
-
-    if use_fused and len(x_slices) < FUSED_NSLICE[fp32_mode]:
-        # the generic loop below has no adaptive widen: materialize the
-        # full split upfront ("auto" state carries only slice 0 initially)
-        from raft_amd._ext import require_ext
-        s_new = torch.empty_like(x_slices[0])
-        require_ext().split_bf16_norms(x.contiguous(), [x_slices[0], s_new], xn)
-        x_slices.append(s_new)
-
+    if _fused_nslice(x, fp32_mode, d) is not None:
+        # X is iteration-invariant: pre-split the bf16 slices and row norms
+        # ONCE (the same caching the reference does for row norms)
+        ops = state if state is not None else kmeans_iter_state(x, fp32_mode)
+        assert ops.x.shape == x.shape, "state= was made for another X"
+        return _FastLoop(ops, centroids.contiguous().clone(), comms,
+                         fp32_mode).run(n_iters)
+    assign = functools.partial(fused_l2nn, x, fp32_mode=fp32_mode,
+                               chunk_rows=chunk_rows)
     inertia_t = None
-    for it in range(n_iters):
-        if use_fused:
-            vx = x if fp32_mode in VERIFY_MODES else None
-            dmin, labels = fused_l2nn_presplit(x_slices, xn, centroids,
-                                               int32_labels=True, verify_x=vx,
-                                               bound=bound)
-        else:
-            dmin, labels = fused_l2nn(x, centroids, fp32_mode=fp32_mode,
-                                      chunk_rows=chunk_rows)
-        # fp32 accumulation regardless of x.dtype (bf16 counts >256 are inexact)
-        acc = torch.float32 if x.dtype in (torch.bfloat16, torch.float16) \
-            else x.dtype
-        sums = reduce_rows_by_key(x, labels, n_keys=k, out_dtype=acc)
-        counts = torch.bincount(labels, minlength=k).to(acc)
-        local_inertia = torch.sum(dmin, dtype=torch.float64).to(acc)
-        packed = torch.cat([sums.reshape(-1), counts, local_inertia.reshape(1)])
-        if comms.get_size() > 1:
-            comms.allreduce(packed, op=ReduceOp.SUM)
-        sums = packed[: k * d].reshape(k, d)
-        counts = packed[k * d: k * d + k]
-        inertia_t = packed[-1]
-        nonzero = counts > 0
-        centroids = torch.where(nonzero.unsqueeze(1),
-                                (sums / counts.clamp_min(1).unsqueeze(1)).to(x.dtype),
-                                centroids)
+    for _ in range(n_iters):
+        centroids, _, inertia_t, _, _ = _lloyd_step(x, centroids, assign, comms)
     # single host sync at the end (a per-iter .item() serializes the pipeline)
     inertia = float(inertia_t.item()) if inertia_t is not None else float("inf")
     return centroids, inertia
 
 
-#: engine chosen by the last adaptive (fp32_mode="auto") _fast_iterate run
+#: engine chosen by the last adaptive (fp32_mode="auto") _FastLoop run
 #: (1 = stayed on bf16x1v, 2 = widened to bf16x2v) — test observability
 _LAST_ADAPTIVE_NSLICE = None
 
 
-def _fast_iterate(x, x_slices, xn, centroids, n_iters, comms, nslice, verify,
-                  bound=(2.0 ** -13, 2.0 ** -18), adaptive=False):
+class _FastLoop:
     """Minimal-dispatch EM loop: every per-iteration stage is ONE kernel
     (centroid split+norms, fused assignment, verify/repair, keyed reduction
     with counts, centroid update) + the rocPRIM label sort + ONE packed
-    allreduce — the per-iter torch-op soup measured ~6-8 ms/step is gone.
+    allreduce.
 
     Multi-GPU (world > 1): SPLIT-BATCH overlap (VERDICT r1 item 8 /
     SURVEY §6) — local rows are split in two halves; half A's packed
@@ -466,128 +454,142 @@ def _fast_iterate(x, x_slices, xn, centroids, n_iters, comms, nslice, verify,
     allreduce(A+B) by linearity, so the update is bitwise the same modulo
     fp32 summation order. Opt out with RAFT_AMD_KMEANS_OVERLAP=0.
 
-    adaptive=True (fp32_mode="auto"): start on the 1-product bf16x1v engine
+    fp32_mode="auto" is adaptive: start on the 1-product bf16x1v engine
     (1/3 the MFMA work), measure the provable-rescan fraction of the FIRST
     iteration (rows whose emulated margin falls inside the wide 2^-7 bound),
     and widen to the 2-slice engine if >2% of rows would rescan. Both
     engines produce the exact fp32 argmin, so the switch is purely a
     performance guard — per-rank decisions need not agree.
     """
-    import os
-    from raft_amd._ext import require_ext
-    from raft_amd.linalg.split_bf16 import SPLIT_BOUND
-    ext = require_ext()
-    k, d = centroids.shape
-    dev = x.device
-    # ANY k takes this path: pad the centroid rows to a 128 multiple with
-    # ZERO vectors whose cn entries are poisoned to +inf after each split —
-    # the sweep can never pick them (score = inf), the verify/rescan kernels
-    # see only the real k rows (centroids[:k] slice), and update leaves the
-    # zero rows untouched (counts 0). Removes the old k % 128 fast-path cliff.
-    pad = (-k) % 128
-    if pad:
-        centroids = torch.cat([centroids,
-                               torch.zeros(pad, d, dtype=centroids.dtype,
-                                           device=dev)])
-    kp = k + pad
-    cur_nslice = 1 if (adaptive and verify) else nslice
-    cur_bound = SPLIT_BOUND[cur_nslice] if (adaptive and verify) else bound
-    frac_t = [None]  # first-iteration provable-rescan fraction (device)
-    c_slices = [torch.empty((kp, d), dtype=torch.bfloat16, device=dev)
-                for _ in range(nslice)]
-    cn = torch.empty(kp, dtype=torch.float32, device=dev)
-    cn_max = torch.zeros(1, dtype=torch.float32, device=dev)
-    world = comms.get_size()
-    # overlap pays when the halves keep the GPU busy longer than the doubled
-    # per-iteration dispatch (~0.5 ms) it costs — gate on shard size
-    # (RAFT_AMD_KMEANS_OVERLAP=1 forces on, =0 off)
-    ov_env = os.environ.get("RAFT_AMD_KMEANS_OVERLAP", "auto")
-    overlap = (world > 1 and x.shape[0] >= 2
-               and (ov_env == "1" or (ov_env != "0"
-                                      and x.shape[0] >= 4_000_000)))
-    if overlap:
-        h = x.shape[0] // 2
-        halves = [(x[:h], [s[:h] for s in x_slices], xn[:h]),
-                  (x[h:], [s[h:] for s in x_slices], xn[h:])]
-    inertia_t = None
 
-    def _local_update(xh, xh_slices, xnh):
+    def __init__(self, ops: KMeansIterState, centroids, comms, fp32_mode):
+        self.ext = require_ext()
+        self.ops, self.comms = ops, comms
+        self.k, self.d = centroids.shape
+        self.verify = fp32_mode in VERIFY_MODES
+        self.adaptive = fp32_mode == "auto"
+        # slices of the mode, and of the engine in use: "auto" starts narrower
+        self.nslice = FUSED_NSLICE[fp32_mode]
+        self.cur_nslice = _AUTO_START_NSLICE if self.adaptive else self.nslice
+        ops.ensure(self.cur_nslice)
+        #: first-iteration provable-rescan fraction (device scalar)
+        self.rescan_frac = None
+        # ANY k takes this path: pad the centroid rows to a 128 multiple with
+        # ZERO vectors whose cn entries are poisoned to +inf after each split —
+        # the sweep can never pick them (score = inf), the verify/rescan kernels
+        # see only the real k rows (centroids[:k] slice), and update leaves the
+        # zero rows untouched (counts 0)
+        self.kp = kp = self.k + (-self.k) % 128
+        if kp > self.k:
+            centroids = torch.cat([centroids, centroids.new_zeros(kp - self.k, self.d)])
+        self.centroids = centroids
+        self.c_slices = [centroids.new_empty((kp, self.d), dtype=torch.bfloat16)
+                         for _ in range(self.nslice)]
+        self.cn = centroids.new_empty(kp)
+        self.cn_max = centroids.new_zeros(1)
+        # overlap pays when the halves keep the GPU busy longer than the doubled
+        # per-iteration dispatch (~0.5 ms) it costs — gate on shard size
+        # (RAFT_AMD_KMEANS_OVERLAP=1 forces on, =0 off)
+        n = ops.x.shape[0]
+        ov_env = os.environ.get("RAFT_AMD_KMEANS_OVERLAP", "auto")
+        self.overlap = (comms.get_size() > 1 and n >= 2
+                        and (ov_env == "1" or (ov_env != "0" and n >= 4_000_000)))
+        self._cut_row_ranges()
+
+    def _cut_row_ranges(self):
+        """(x, slices, xn) per row range: the two halves under overlap, else
+        the whole shard. Cut again whenever ops gains a slice."""
+        ops, h = self.ops, self.ops.x.shape[0] // 2
+        cuts = [slice(0, h), slice(h, None)] if self.overlap else [slice(None)]
+        self.row_ranges = [(ops.x[c], [s[c] for s in ops.slices], ops.xn[c])
+                           for c in cuts]
+
+    def _split_centroids(self):
+        self.ext.split_bf16_norms(self.centroids, self.c_slices[:self.cur_nslice],
+                                  self.cn, self.cn_max)
+        if self.kp > self.k:
+            # poison the padding rows' norms AFTER the split (their zero
+            # vectors leave the fused cn_max untouched): sweep score = +inf
+            self.cn[self.k:].fill_(float("inf"))
+
+    def _local_update(self, xh, xh_slices, xnh):
         """assignment + keyed reduction for one row range -> packed buffer"""
-        dmin, amin, dmin2 = ext.fused_l2nn_split(list(xh_slices[:cur_nslice]),
-                                                 c_slices[:cur_nslice], xnh, cn)
-        if adaptive and frac_t[0] is None:
+        ext, k, kp, d = self.ext, self.k, self.kp, self.d
+        lead, tail = SPLIT_BOUND[self.cur_nslice]
+        dmin, amin, dmin2 = ext.fused_l2nn_split(xh_slices[:self.cur_nslice],
+                                                 self.c_slices[:self.cur_nslice],
+                                                 xnh, self.cn)
+        if self.adaptive and self.rescan_frac is None:
             # pre-repair margin stats (dmin is overwritten by the verify
             # kernel below): fraction of rows the exact rescan will touch
-            lead_, tail_ = cur_bound
-            b = 2.0 * (lead_ * (xnh * cn_max).clamp_min(0).sqrt()
-                       + tail_ * (xnh + cn_max))
-            frac_t[0] = ((dmin2 - dmin) < b).float().mean()
+            b = 2.0 * (lead * (xnh * self.cn_max).clamp_min(0).sqrt()
+                       + tail * (xnh + self.cn_max))
+            self.rescan_frac = ((dmin2 - dmin) < b).float().mean()
         keys_sorted, perm = torch.sort(amin)
-        packed = torch.zeros(kp * d + kp + 1, dtype=torch.float32, device=dev)
+        packed = torch.zeros(kp * d + kp + 1, dtype=torch.float32, device=xh.device)
         sums = packed[: kp * d].view(kp, d)
         counts = packed[kp * d: kp * d + kp]
-        if verify:
+        if self.verify:
             # ONE X pass: centroid-sum accumulation + exact-fp32
             # verify/refine + the inertia fold (sum of the FINAL repaired
             # distances accumulates into packed[-1] in-kernel); cn_max comes
             # fused out of split_bf16_norms. centroids[:k]: the rescan must
             # only see the REAL rows (the zero padding rows would win it)
             ext.kmeans_update_verify(xh, perm.to(torch.int32), keys_sorted,
-                                     centroids[:k], xnh, dmin, amin, dmin2,
-                                     cn_max, sums, counts, packed[-1:],
-                                     lead=cur_bound[0], tail=cur_bound[1])
+                                     self.centroids[:k], xnh, dmin, amin, dmin2,
+                                     self.cn_max, sums, counts, packed[-1:],
+                                     lead=lead, tail=tail)
         else:
-            ext.reduce_rows_by_key_sorted_into(xh, perm.to(torch.int32),
-                                               keys_sorted, sums, counts,
-                                               dmin, packed[-1:])
+            ext.reduce_rows_by_key_sorted_into(xh, perm.to(torch.int32), keys_sorted,
+                                               sums, counts, dmin, packed[-1:])
         return packed
 
-    for it in range(n_iters):
-        ext.split_bf16_norms(centroids, c_slices[:cur_nslice], cn, cn_max)
-        if pad:
-            # poison the padding rows' norms AFTER the split (their zero
-            # vectors leave the fused cn_max untouched): sweep score = +inf
-            cn[k:].fill_(float("inf"))
-        if overlap:
-            packed_a = _local_update(*halves[0])
-            work_a = comms.allreduce_async(packed_a, op=ReduceOp.SUM)
-            packed_b = _local_update(*halves[1])
-            work_b = comms.allreduce_async(packed_b, op=ReduceOp.SUM)
-            if work_a is not None:
-                work_a.wait()
-            if work_b is not None:
-                work_b.wait()
-            packed = packed_a
-            packed += packed_b
-        else:
-            packed = _local_update(x, x_slices, xn)
-            if world > 1:
+    def _combine(self):
+        """Every row range's packed buffer, summed over ranges and ranks."""
+        comms = self.comms
+        if not self.overlap:
+            packed = self._local_update(*self.row_ranges[0])
+            if comms.get_size() > 1:
                 comms.allreduce(packed, op=ReduceOp.SUM)
-        sums = packed[: kp * d].view(kp, d)
-        counts = packed[kp * d: kp * d + kp]
-        ext.kmeans_update_centroids(sums, counts, centroids)
-        inertia_t = packed[-1]
-        if adaptive and it == 0 and frac_t[0] is not None:
-            # one host sync, once: widen to the tight-bound 2-slice engine
-            # if the wide bf16x1v bound would rescan >2% of rows each iter
-            if nslice >= 2 and float(frac_t[0].item()) > 0.02:
-                while len(x_slices) < nslice:
-                    # lazily materialize the residual slice (auto state
-                    # starts 1-slice); recomputes slice 0/xn with identical
-                    # values in the same fused pass
-                    s_new = torch.empty_like(x_slices[0])
-                    ext.split_bf16_norms(x.contiguous(),
-                                         [x_slices[0], s_new], xn)
-                    x_slices.append(s_new)
-                if overlap:
-                    halves = [(x[:h], [s[:h] for s in x_slices], xn[:h]),
-                              (x[h:], [s[h:] for s in x_slices], xn[h:])]
-                cur_nslice, cur_bound = nslice, bound
-            adaptive = False
-            global _LAST_ADAPTIVE_NSLICE
-            _LAST_ADAPTIVE_NSLICE = cur_nslice
-    inertia = float(inertia_t.item()) if inertia_t is not None else float("inf")
-    return centroids[:k] if pad else centroids, inertia
+            return packed
+        packed_a = self._local_update(*self.row_ranges[0])
+        work_a = comms.allreduce_async(packed_a, op=ReduceOp.SUM)
+        packed_b = self._local_update(*self.row_ranges[1])
+        work_b = comms.allreduce_async(packed_b, op=ReduceOp.SUM)
+        for work in (work_a, work_b):
+            if work is not None:
+                work.wait()
+        packed_a += packed_b
+        return packed_a
+
+    def _update_centroids(self, packed):
+        kp, d = self.kp, self.d
+        self.ext.kmeans_update_centroids(packed[: kp * d].view(kp, d),
+                                         packed[kp * d: kp * d + kp],
+                                         self.centroids)
+
+    def _decide_widen(self):
+        """Once, after the first adaptive iteration (one host sync): widen to
+        the tight-bound 2-slice engine if the wide bf16x1v bound would rescan
+        >2% of rows each iteration."""
+        global _LAST_ADAPTIVE_NSLICE
+        if self.nslice > self.cur_nslice and float(self.rescan_frac.item()) > 0.02:
+            self.ops.ensure(self.nslice)
+            self._cut_row_ranges()
+            self.cur_nslice = self.nslice
+        self.adaptive = False
+        _LAST_ADAPTIVE_NSLICE = self.cur_nslice
+
+    def run(self, n_iters):
+        packed = None
+        for _ in range(n_iters):
+            self._split_centroids()
+            packed = self._combine()
+            self._update_centroids(packed)
+            if self.adaptive:
+                self._decide_widen()
+        inertia = float(packed[-1].item()) if packed is not None else float("inf")
+        return self.centroids[:self.k], inertia
 
 
 def kmeans_predict(model_or_centroids, x: torch.Tensor, fp32_mode: str = "auto") -> torch.Tensor:
@@ -612,12 +614,7 @@ def kmeans_balanced_fit(x: torch.Tensor, n_clusters: int, max_iter: int = 20,
     """
     n = x.shape[0]
     n_sample = max(n_clusters * 4, int(n * sample_fraction))
-    if n_sample < n:
-        from raft_amd.matrix.sample_rows import sample_rows
-        from raft_amd.random.rng import RngState as _RS
-        xs = sample_rows(x, n_sample, state=_RS(seed=seed))
-    else:
-        xs = x
+    xs = sample_rows(x, n_sample, state=RngState(seed=seed)) if n_sample < n else x
     model = kmeans_fit(xs, KMeansParams(n_clusters=n_clusters, max_iter=max_iter,
                                         seed=seed, init="random",
                                         fp32_mode=fp32_mode))
