@@ -41,7 +41,7 @@ def main():
     p.add_argument("--rows", type=int, default=10_000_000)
     p.add_argument("--dim", type=int, default=256)
     p.add_argument("--k", type=int, default=1024)
-    p.add_argument("--variants", type=str, default="2d:8,2d_xreg:8")
+    p.add_argument("--variants", type=str, default="2d:8,2d_xreg:8,2d_xring:8")
     p.add_argument("--update-verify", action="store_true")
     p.add_argument("--window", type=float, default=1.0)
     p.add_argument("--repeats", type=int, default=5)

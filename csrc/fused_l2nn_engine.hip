@@ -15,6 +15,7 @@ namespace {
 struct L2nnEnv {
   char mode_2d, mode_256;  // '0' off, '1' wherever the shape allows, else auto
   char mode_xreg;          // '0' off, '1' on, else the measured default
+  char mode_xring;         // '0' off, '1' on, else the measured default
   char w8;                 // '0' off, '2' for every nslice, else 3-slice only
   int gt;                  // 1, 2, 4 or 8; 0 = per-nslice default
   bool bk32, adirect, db, phased, persist;
@@ -30,6 +31,7 @@ const L2nnEnv& l2nn_env() {
     v.mode_2d = first("RAFT_AMD_L2NN_2D");
     v.mode_256 = first("RAFT_AMD_L2NN_256");
     v.mode_xreg = first("RAFT_AMD_L2NN_XREG");
+    v.mode_xring = first("RAFT_AMD_L2NN_XRING");
     v.w8 = first("RAFT_AMD_L2NN_W8");
     const char* g = getenv("RAFT_AMD_L2NN_GT");
     v.gt = g ? atoi(g) : 0;
@@ -46,11 +48,16 @@ const L2nnEnv& l2nn_env() {
 
 constexpr const char* kEngineNames[] = {"auto",      "v1",      "v1_db", "v1_phased",
                                         "2d",        "2d_phased", "2d_bk32", "2d_ad",
-                                        "256",       "w8",      "persist", "2d_xreg"};
+                                        "256",       "w8",      "persist", "2d_xreg",
+                                        "2d_xring"};
 
 // auto picks 2d_xreg over 2d where both fit: 5.47 against 7.61 ms at
 // 10M x 256 k=1024, one process, alternating
 constexpr bool kXregDefault = true;
+
+// auto picks 2d_xring over 2d_xreg: 4.94 against 5.16 ms at 10M x 256 k=1024,
+// one process, alternating
+constexpr bool kXringDefault = true;
 
 bool is_2d(L2nnEngine e) {
   return e == L2nnEngine::TwoD || e == L2nnEngine::TwoDPhased ||
@@ -82,6 +89,7 @@ const char* l2nn_engine_violation(L2nnEngine e, int nslice, int n, int d) {
       if (d > 256) return "d must be at most 256 (X stays in LDS)";
       return nullptr;
     case L2nnEngine::TwoDXreg:
+    case L2nnEngine::TwoDXring:
       if (nslice != 1) return "nslice must be 1";
       if (d > 256) return "d must be at most 256 (X stays in registers)";
       return nullptr;
@@ -106,6 +114,13 @@ bool l2nn_xreg_wanted() {
   return mode != '0' && (mode == '1' || kXregDefault);
 }
 
+// 2d_xring takes 2d_xreg's shapes where it is wanted; RAFT_AMD_L2NN_XRING=0
+// gives them back, =1 takes them whatever the default
+bool l2nn_xring_wanted() {
+  const char mode = l2nn_env().mode_xring;
+  return mode != '0' && (mode == '1' || kXringDefault);
+}
+
 // w8 wins only for NSLICE=3 (staging-bound: halved X re-reads beat the lost
 // cross-block barrier overlap); the 4-wave 2-block v1 kernel wins for
 // NSLICE<=2 (34.3 vs 38.0 ms/step at 10M x 256 k=1024). RAFT_AMD_L2NN_W8=2
@@ -127,7 +142,8 @@ L2nnEngine l2nn_auto_engine(int nslice, long long m, int n, int d) {
     // 10M x 1024 d=256). Kept as the base for future schedule work.
     if (env.mode_256 == '1' && fits(L2nnEngine::E256)) return L2nnEngine::E256;
     if (l2nn_2d_wanted(nslice, m, n)) {
-      if (l2nn_xreg_wanted() && fits(L2nnEngine::TwoDXreg)) return L2nnEngine::TwoDXreg;
+      if (l2nn_xreg_wanted() && fits(L2nnEngine::TwoDXreg))
+        return l2nn_xring_wanted() ? L2nnEngine::TwoDXring : L2nnEngine::TwoDXreg;
       if (env.bk32) return L2nnEngine::TwoDBk32;
       if (env.adirect) return L2nnEngine::TwoDAd;
       return env.phased && nslice == 2 ? L2nnEngine::TwoDPhased : L2nnEngine::TwoD;
@@ -174,7 +190,8 @@ L2nnPlan l2nn_resolve_engine(int nslice, long long m, int n, int d,
     while (gt > 1 && tiles % gt != 0) gt >>= 1;
     plan.gt = gt;
     plan.n_groups = tiles / gt;
-  } else if (plan.engine == L2nnEngine::TwoDXreg) {
+  } else if (plan.engine == L2nnEngine::TwoDXreg ||
+             plan.engine == L2nnEngine::TwoDXring) {
     // same rule as the 1-slice 2d default; a single group writes the result
     // itself and needs no partials
     if (gt == 0) gt = l2nn_env().gt;
@@ -200,6 +217,8 @@ void launch_fused_l2nn(const L2nnPlan& plan, const void** xsl, const void** csl,
                    plan.engine, plan.gt, stream);
   else if (plan.engine == L2nnEngine::TwoDXreg)
     launch_l2nn_xreg(p, xn, cn, pd, pd2, pi, dmin, amin, dmin2, m, n, d, plan.gt, stream);
+  else if (plan.engine == L2nnEngine::TwoDXring)
+    launch_l2nn_xring(p, xn, cn, pd, pd2, pi, dmin, amin, dmin2, m, n, d, plan.gt, stream);
   else if (plan.engine == L2nnEngine::E256)
     launch_l2nn_256(p, xn, cn, pd, pd2, pi, dmin, amin, dmin2, m, n, d, nslice, stream);
   else if (plan.engine == L2nnEngine::W8)

@@ -23,6 +23,7 @@ enum class L2nnEngine {
   W8,          // "w8": fused_l2nn_w8_kernel (128 x 256 tile, 8 waves)
   Persist,     // "persist": fused_l2nn_persist_kernel (best only)
   TwoDXreg,    // "2d_xreg": fused_l2nn_xreg_kernel (1 slice, X in registers)
+  TwoDXring,   // "2d_xring": fused_l2nn_xring_kernel (2d_xreg, counted C ring)
 };
 
 const char* l2nn_engine_name(L2nnEngine e);
@@ -61,6 +62,9 @@ void launch_l2nn_2d(const SlicePtrs& p, const float* xn, const float* cn, float*
 void launch_l2nn_xreg(const SlicePtrs& p, const float* xn, const float* cn, float* pd,
                       float* pd2, int* pi, float* dmin, int* amin, float* dmin2,
                       long long m, int n, int d, int gt, hipStream_t stream);
+void launch_l2nn_xring(const SlicePtrs& p, const float* xn, const float* cn, float* pd,
+                       float* pd2, int* pi, float* dmin, int* amin, float* dmin2,
+                       long long m, int n, int d, int gt, hipStream_t stream);
 void launch_l2nn_256(const SlicePtrs& p, const float* xn, const float* cn, float* pd,
                      float* pd2, int* pi, float* dmin, int* amin, float* dmin2,
                      long long m, int n, int d, int nslice, hipStream_t stream);

@@ -52,6 +52,24 @@ __device__ __forceinline__ void top2_push(float& best, float& best2, int& idx,
 // added at the final write — it does not move the argmin). col0 is this
 // lane's column at fragment 0; fragment fc is col0 + fc*16, and its norm
 // depends only on fc (CF loads per tile, not RF*4*CF).
+// The norms arrive in registers: cn_r[fc] is ||c||^2 of column col0 + fc*16.
+template <int RF, int CF>
+__device__ __forceinline__ void top2_fold_tile_cn(const f32x4 (&acc)[RF][CF],
+                                                  const float (&cn_r)[CF], int col0,
+                                                  float (&best)[RF][4],
+                                                  float (&best2)[RF][4],
+                                                  int (&bidx)[RF][4]) {
+#pragma unroll
+  for (int fr = 0; fr < RF; fr++)
+#pragma unroll
+    for (int reg = 0; reg < 4; reg++)
+#pragma unroll
+      for (int fc = 0; fc < CF; fc++)
+        top2_push(best[fr][reg], best2[fr][reg], bidx[fr][reg],
+                  cn_r[fc] - 2.f * acc[fr][fc][reg], col0 + fc * 16);
+}
+
+// ... and the same with the norms read from global memory
 template <int RF, int CF>
 __device__ __forceinline__ void top2_fold_tile(const f32x4 (&acc)[RF][CF],
                                                const float* __restrict__ cn,
@@ -61,14 +79,7 @@ __device__ __forceinline__ void top2_fold_tile(const f32x4 (&acc)[RF][CF],
   float cn_r[CF];
 #pragma unroll
   for (int fc = 0; fc < CF; fc++) cn_r[fc] = cn[col0 + fc * 16];
-#pragma unroll
-  for (int fr = 0; fr < RF; fr++)
-#pragma unroll
-    for (int reg = 0; reg < 4; reg++)
-#pragma unroll
-      for (int fc = 0; fc < CF; fc++)
-        top2_push(best[fr][reg], best2[fr][reg], bidx[fr][reg],
-                  cn_r[fc] - 2.f * acc[fr][fc][reg], col0 + fc * 16);
+  top2_fold_tile_cn(acc, cn_r, col0, best, best2, bidx);
 }
 
 // merge candidate (b, b2, bi) into (v, v2, vi). Plain: the two sides cover
