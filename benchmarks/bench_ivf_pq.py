@@ -1,0 +1,104 @@
+#!/usr/bin/env python3
+"""IVF-PQ against IVF-Flat on one data set and one n_probes: 1M x 128 fp32
+make_blobs rows (1024 centers), n_lists = 1024, 10,000 held-out queries.
+
+It reports
+  * the build time of both indices (IVF-PQ: coarse k-means, codebook training,
+    encode, packing) and the bytes per row they store,
+  * queries per second of the whole ivf_pq_search and ivf_flat_search calls at
+    k = 10 and the given n_probes,
+  * recall@10 of both against the brute-force ids. IVF-PQ ranks by the
+    distance to the reconstructed rows and is NOT re-ranked here.
+
+Method (as bench_ivf_flat.py): every call is warmed at the timed shape; a timed
+window is synchronised on both sides and holds --reps calls; --rounds windows,
+the two indices alternating inside a round; median and min..max printed. One
+JSON line.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--rows", type=int, default=1_000_000)
+    p.add_argument("--dim", type=int, default=128)
+    p.add_argument("--queries", type=int, default=10_000)
+    p.add_argument("--n-lists", type=int, default=1024)
+    p.add_argument("--pq-dim", type=int, default=0)
+    p.add_argument("--n-probes", type=int, default=32)
+    p.add_argument("--k", type=int, default=10)
+    p.add_argument("--reps", type=int, default=3)
+    p.add_argument("--rounds", type=int, default=3)
+    args = p.parse_args()
+
+    assert torch.cuda.is_available(), "this benchmark measures the GPU"
+    dev = torch.device("cuda")
+    from raft_amd.neighbors import (BruteForceIndex, IvfFlatParams, IvfPqParams,
+                                    ivf_flat_build, ivf_flat_search, ivf_pq_build,
+                                    ivf_pq_search)
+    from raft_amd.random import RngState, make_blobs
+
+    n, d, nq, k, n_probes = args.rows, args.dim, args.queries, args.k, args.n_probes
+
+    def sync_time(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = f()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    allx, _, _ = make_blobs(n + nq, d, n_clusters=1024, state=RngState(seed=7), device=dev)
+    allx = allx[torch.randperm(n + nq, device=dev,
+                               generator=torch.Generator(dev).manual_seed(1))]
+    x, q = allx[:n].contiguous(), allx[n:].contiguous()
+    del allx
+
+    warm = x[:max(args.n_lists * 8, n // 16)]
+    ivf_flat_build(warm, IvfFlatParams(n_lists=args.n_lists))
+    flat_s, flat = sync_time(lambda: ivf_flat_build(x, IvfFlatParams(n_lists=args.n_lists)))
+    pq_params = IvfPqParams(n_lists=args.n_lists, pq_dim=args.pq_dim)
+    ivf_pq_build(warm, pq_params)
+    pq_s, pq = sync_time(lambda: ivf_pq_build(x, pq_params))
+    print(f"# built: flat {flat_s:.2f} s, pq {pq_s:.2f} s (pq_dim {pq.pq_dim})",
+          file=sys.stderr, flush=True)
+
+    calls = {"ivf_pq": lambda: ivf_pq_search(pq, q, k, n_probes),
+             "ivf_flat": lambda: ivf_flat_search(flat, q, k, n_probes)}
+    bf_ids = BruteForceIndex(x).search(q, k)[1]
+    out = {"metric": "IVF-PQ vs IVF-Flat, queries per second", "data": "blobs", "rows": n,
+           "dim": d, "queries": nq, "n_lists": args.n_lists, "n_probes": n_probes, "k": k,
+           "reps": args.reps, "rounds": args.rounds,
+           "ivf_pq": {"build_s": round(pq_s, 3), "pq_dim": pq.pq_dim, "pq_len": pq.pq_len,
+                      "bytes_per_row": pq.pq_dim_pad},
+           "ivf_flat": {"build_s": round(flat_s, 3), "bytes_per_row": 4 * flat.d_pad}}
+    times = {name: [] for name in calls}
+    for name, f in calls.items():
+        ids = f()[1]                                          # warm this shape
+        hit = 0
+        for s in range(0, nq, 1024):
+            hit += int((ids[s:s + 1024, :, None] == bf_ids[s:s + 1024, None, :])
+                       .any(dim=2).sum())
+        out[name]["recall"] = round(hit / (nq * k), 4)
+    for _ in range(args.rounds):
+        for name, f in calls.items():                         # alternate
+            t, _ = sync_time(lambda: [f() for _ in range(args.reps)])
+            times[name].append(t / args.reps)
+    for name, ts in times.items():
+        out[name].update(qps_median=round(nq / statistics.median(ts)),
+                         qps_min=round(nq / max(ts)), qps_max=round(nq / min(ts)))
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -17,6 +17,12 @@ ROOT = Path(__file__).resolve().parent
 CSRC = ROOT / "csrc"
 BUILD = ROOT / "build" / "ext"
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
+#: extra hipcc flags of single sources (CMakeLists.txt carries the same):
+#: ivf_pq.hip is compiled without the packed fp32 instructions, all its fp32
+#: arithmetic is scalar per lane
+SOURCE_FLAGS = {
+    "ivf_pq.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
 
 
 def _torch_flags():
@@ -61,7 +67,8 @@ def build(verbose: bool = True) -> Path:
         if obj.exists() and obj.stat().st_mtime > max(src.stat().st_mtime,
                                                       headers_mtime):
             continue
-        cmd = ["hipcc", "-c", "-x", "hip", str(src), "-o", str(obj)] + common
+        cmd = (["hipcc", "-c", "-x", "hip", str(src), "-o", str(obj)] + common
+               + SOURCE_FLAGS.get(src.name, []))
         if verbose:
             print("[build_ext] compile", src.name, flush=True)
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE,

@@ -133,6 +133,15 @@ void launch_ivf_flat_scan(const void*, bool, const long long*, const long long*,
                           const long long*, const unsigned int*, long long, float*,
                           long long, long long, long long, long long, long long,
                           long long, int, int, int, int, hipStream_t);
+// from ivf_pq.hip
+void launch_ivf_pq_encode(const float*, const long long*, const float*, const float*,
+                          unsigned char*, long long, long long, int, int, int, hipStream_t);
+size_t ivf_pq_scan_lds_bytes(int, int);
+void launch_ivf_pq_scan(const unsigned char*, const long long*, const long long*,
+                        const float*, const float*, const float*, const long long*,
+                        const long long*, const unsigned int*, long long, float*, long long,
+                        long long, long long, long long, int, int, int, int, int, int,
+                        hipStream_t);
 // from gemm_rocblas.cpp
 void gemm_bf16_f32_rowmajor(const void*, const void*, float*, long long, long long,
                             long long, float, void*);
@@ -1003,6 +1012,105 @@ void ivf_flat_scan(torch::Tensor data, torch::Tensor list_offsets, torch::Tensor
       cur_stream());
 }
 
+// (pq_dim, pq_len) of codebooks [pq_dim, pq_len, 256] for rows of d features
+static std::pair<int, int> ivf_pq_shape(const torch::Tensor& centroids,
+                                        const torch::Tensor& codebooks, long long d,
+                                        const char* who) {
+  TORCH_CHECK(centroids.is_cuda() && centroids.is_contiguous() && centroids.dim() == 2 &&
+              centroids.scalar_type() == torch::kFloat32 && centroids.size(0) >= 1 &&
+              centroids.size(1) == d,
+              who, ": centroids must be contiguous fp32 [n_lists, ", d, "]");
+  TORCH_CHECK(codebooks.is_cuda() && codebooks.is_contiguous() && codebooks.dim() == 3 &&
+              codebooks.scalar_type() == torch::kFloat32 && codebooks.size(2) == 256 &&
+              codebooks.size(0) >= 1 && codebooks.size(0) <= d &&
+              codebooks.size(1) == (d + codebooks.size(0) - 1) / codebooks.size(0),
+              who, ": codebooks must be contiguous fp32 [pq_dim, ceil(d / pq_dim), 256] "
+              "with pq_dim in [1, d]");
+  return {(int)codebooks.size(0), (int)codebooks.size(1)};
+}
+
+// IVF-PQ encode: the nearest codebook entry of every subspace of the residual
+// x - centroids[labels]; codes [n, pq_dim_pad] uint8 is written in full.
+void ivf_pq_encode(torch::Tensor x, torch::Tensor labels, torch::Tensor centroids,
+                   torch::Tensor codebooks, torch::Tensor codes) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2 &&
+              x.scalar_type() == torch::kFloat32 && x.size(1) >= 1,
+              "ivf_pq_encode: x must be contiguous fp32 [n, d]");
+  const long long n = x.size(0), d = x.size(1);
+  const auto [pq_dim, pq_len] = ivf_pq_shape(centroids, codebooks, d, "ivf_pq_encode");
+  TORCH_CHECK(pq_len <= 32, "ivf_pq_encode: pq_len must be <= 32");
+  TORCH_CHECK(labels.is_cuda() && labels.is_contiguous() &&
+              labels.scalar_type() == torch::kInt64 && labels.dim() == 1 &&
+              labels.numel() == n,
+              "ivf_pq_encode: labels must be a contiguous int64 GPU tensor [n]");
+  const long long pq_dim_pad = (pq_dim + 15) / 16 * 16;
+  TORCH_CHECK(codes.is_cuda() && codes.is_contiguous() &&
+              codes.scalar_type() == torch::kUInt8 && codes.dim() == 2 &&
+              codes.size(0) == n && codes.size(1) == pq_dim_pad,
+              "ivf_pq_encode: codes must be contiguous uint8 [n, ", pq_dim_pad, "]");
+  raft_amd::launch_ivf_pq_encode(
+      x.data_ptr<float>(), reinterpret_cast<const long long*>(labels.data_ptr<int64_t>()),
+      centroids.data_ptr<float>(), codebooks.data_ptr<float>(), codes.data_ptr<uint8_t>(), n,
+      centroids.size(0), (int)d, pq_dim, pq_len, cur_stream());
+}
+
+// IVF-PQ pair-major LUT scan of one query chunk into the ragged candidate
+// buffer `out`: every padded row of every probed list is written. probes and
+// pair_out_off are [q, n_probes] in probe order.
+void ivf_pq_scan(torch::Tensor codes, torch::Tensor list_offsets, torch::Tensor indices,
+                 torch::Tensor queries, torch::Tensor centroids, torch::Tensor codebooks,
+                 torch::Tensor probes, torch::Tensor pair_out_off,
+                 c10::optional<torch::Tensor> filter_words, int64_t filter_bits,
+                 torch::Tensor out, int64_t metric, int64_t y_split) {
+  const auto i64 = [](const torch::Tensor& t, long long numel, const char* what) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kInt64 && t.is_contiguous() &&
+                t.numel() == numel,
+                "ivf_pq_scan: ", what, " must be a contiguous int64 GPU tensor of ", numel,
+                " elements");
+    return reinterpret_cast<const long long*>(t.data_ptr<int64_t>());
+  };
+  TORCH_CHECK(queries.is_cuda() && queries.is_contiguous() && queries.dim() == 2 &&
+              queries.scalar_type() == torch::kFloat32 && queries.size(1) >= 1,
+              "ivf_pq_scan: queries must be contiguous fp32 [q, d]");
+  const long long nq = queries.size(0), d = queries.size(1);
+  const auto [pq_dim, pq_len] = ivf_pq_shape(centroids, codebooks, d, "ivf_pq_scan");
+  const long long pq_dim_pad = (pq_dim + 15) / 16 * 16;
+  TORCH_CHECK(raft_amd::ivf_pq_scan_lds_bytes(pq_dim, pq_len) <= 160 * 1024 - 16,
+              "ivf_pq_scan: the look-up table does not fit 160 KiB of LDS");
+  const long long total_rows = indices.numel();
+  TORCH_CHECK(codes.is_cuda() && codes.is_contiguous() && codes.dim() == 1 &&
+              codes.scalar_type() == torch::kUInt8 && total_rows % 64 == 0 &&
+              codes.numel() == total_rows * pq_dim_pad &&
+              reinterpret_cast<uintptr_t>(codes.data_ptr()) % 16 == 0,
+              "ivf_pq_scan: codes must be a flat, 16-byte aligned uint8 GPU tensor of "
+              "indices.numel() rows of pq_dim_pad bytes, the row count a multiple of 64");
+  const long long n_lists = centroids.size(0);
+  TORCH_CHECK(probes.dim() == 2 && probes.size(0) == nq && probes.size(1) >= 1 &&
+              probes.size(1) <= 2147483647ll,
+              "ivf_pq_scan: probes must be int64 [q, n_probes]");
+  const long long n_pairs = probes.numel();
+  const long long* lo = i64(list_offsets, n_lists + 1, "list_offsets");
+  const long long* idx = i64(indices, total_rows, "indices");
+  const long long* pr = i64(probes, n_pairs, "probes");
+  const long long* po = i64(pair_out_off, n_pairs, "pair_out_off");
+  TORCH_CHECK(out.is_cuda() && out.is_contiguous() && out.dim() == 1 &&
+              out.scalar_type() == torch::kFloat32,
+              "ivf_pq_scan: out must be a flat contiguous fp32 GPU tensor");
+  const unsigned int* fw = nullptr;
+  if (filter_words.has_value()) {
+    const torch::Tensor& f = filter_words.value();
+    TORCH_CHECK(f.is_cuda() && f.scalar_type() == torch::kInt32 && f.is_contiguous() &&
+                f.dim() == 1 && filter_bits >= 0 && f.numel() * 32 >= filter_bits,
+                "ivf_pq_scan: filter must be int32 words covering filter_bits");
+    fw = reinterpret_cast<const unsigned int*>(f.data_ptr<int>());
+  }
+  raft_amd::launch_ivf_pq_scan(
+      codes.data_ptr<uint8_t>(), lo, idx, queries.data_ptr<float>(),
+      centroids.data_ptr<float>(), codebooks.data_ptr<float>(), pr, po, fw, filter_bits,
+      out.data_ptr<float>(), out.numel(), n_lists, total_rows, nq, (int)probes.size(1),
+      (int)d, pq_dim, pq_len, (int)metric, (int)y_split, cur_stream());
+}
+
 void bitmap_row_degrees(torch::Tensor bitmap, torch::Tensor deg) {
   const unsigned int* bm = bitmap_words(bitmap, "bitmap_row_degrees");
   TORCH_CHECK(deg.is_cuda() && deg.scalar_type() == torch::kInt64 &&
@@ -1431,6 +1539,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ivf_flat_scan_max_qg", [](int64_t d_pad) {
     return (int64_t)raft_amd::ivf_flat_scan_max_qg((int)d_pad);
   }, "largest query-group size whose staged queries fit the scan kernel's LDS");
+  m.def("ivf_pq_encode", &ivf_pq_encode,
+        "IVF-PQ: nearest codebook entry per subspace of x - centroids[labels]",
+        pybind11::arg("x"), pybind11::arg("labels"), pybind11::arg("centroids"),
+        pybind11::arg("codebooks"), pybind11::arg("codes"));
+  m.def("ivf_pq_scan", &ivf_pq_scan,
+        "IVF-PQ pair-major LUT scan of the probed lists into a ragged candidate buffer",
+        pybind11::arg("codes"), pybind11::arg("list_offsets"), pybind11::arg("indices"),
+        pybind11::arg("queries"), pybind11::arg("centroids"), pybind11::arg("codebooks"),
+        pybind11::arg("probes"), pybind11::arg("pair_out_off"),
+        pybind11::arg("filter_words"), pybind11::arg("filter_bits"), pybind11::arg("out"),
+        pybind11::arg("metric"), pybind11::arg("y_split"));
   m.def("bitmap_row_degrees", &bitmap_row_degrees,
         "per-row popcount of a row-padded bitmap into an int64 vector");
   m.def("bitmap_rows_to_csr", &bitmap_rows_to_csr,

@@ -119,4 +119,33 @@ void launch_ivf_flat_scan(const void* data, bool data_bf16,
                           long long max_items, int d, int metric, int qg, int y_split,
                           hipStream_t s);
 
+// IVF-PQ (csrc/ivf_pq.hip), 8-bit codes. codebooks is fp32
+// [pq_dim][pq_len][256] (entry-minor), pq_len = ceil(d / pq_dim), features
+// past d are zero; pq_dim_pad = pq_dim rounded up to 16.
+//
+// Encode: codes[n][pq_dim_pad] (row-major, pad bytes 0) gets, per subspace,
+// the entry nearest to the residual x - centroids[labels[row]] (unexpanded
+// fp32 sum, exact ties to the smallest entry); a row whose label is outside
+// [0, n_lists) gets code 0. pq_len <= 32.
+void launch_ivf_pq_encode(const float* x, const long long* labels, const float* centroids,
+                          const float* codebooks, unsigned char* codes, long long n,
+                          long long n_lists, int d, int pq_dim, int pq_len, hipStream_t s);
+// Scan, pair-major: pair p = query p / n_probes, list probes[p], one
+// look-up table in LDS per block; ivf_pq_scan_lds_bytes must not exceed
+// 160 KiB less 16 bytes, else the launcher throws. codes is the IVF-Flat
+// interleaved layout with byte elements (16 codes per chunk, 16-byte aligned);
+// list_offsets / indices / filter / out / metric as in launch_ivf_flat_scan,
+// with pair_out_off[p] in probe order. Distances are to the reconstructed
+// rows centroid + decoded residual. y_split blocks share a list's groups and
+// each rebuilds the table.
+size_t ivf_pq_scan_lds_bytes(int pq_dim, int pq_len);
+void launch_ivf_pq_scan(const unsigned char* codes, const long long* list_offsets,
+                        const long long* indices, const float* queries,
+                        const float* centroids, const float* codebooks,
+                        const long long* probes, const long long* pair_out_off,
+                        const unsigned int* filter_words, long long filter_bits, float* out,
+                        long long out_numel, long long n_lists, long long total_rows,
+                        long long n_queries, int n_probes, int d, int pq_dim, int pq_len,
+                        int metric, int y_split, hipStream_t s);
+
 }  // namespace raft_amd
