@@ -8,12 +8,17 @@ It reports
   * queries per second of the whole ivf_pq_search and ivf_flat_search calls at
     k = 10 and the given n_probes,
   * recall@10 of both against the brute-force ids. IVF-PQ ranks by the
-    distance to the reconstructed rows and is NOT re-ranked here.
+    distance to the reconstructed rows; the plain search is NOT re-ranked,
+  * per --refine-ratio r: queries per second and recall@10 of
+    ivf_pq_search(..., dataset=x, refine_ratio=r), and the time of refine alone
+    on that search's k * r candidates with engine="kernel" and engine="torch"
+    (and the share of result slots in which the two return the same id).
 
 Method (as bench_ivf_flat.py): every call is warmed at the timed shape; a timed
-window is synchronised on both sides and holds --reps calls; --rounds windows,
-the two indices alternating inside a round; median and min..max printed. One
-JSON line.
+window is synchronised on both sides and holds --reps calls (--refine-reps of
+refine alone); --rounds windows,
+the calls alternating inside a round; median and min..max printed. One JSON
+line.
 """
 from __future__ import annotations
 
@@ -38,6 +43,9 @@ def main():
     p.add_argument("--pq-dim", type=int, default=0)
     p.add_argument("--n-probes", type=int, default=32)
     p.add_argument("--k", type=int, default=10)
+    p.add_argument("--refine-ratio", type=int, nargs="*", default=[1, 2, 4])
+    p.add_argument("--refine-reps", type=int, default=200,
+                   help="calls in one timed window of refine alone (a call is short)")
     p.add_argument("--reps", type=int, default=3)
     p.add_argument("--rounds", type=int, default=3)
     args = p.parse_args()
@@ -46,7 +54,7 @@ def main():
     dev = torch.device("cuda")
     from raft_amd.neighbors import (BruteForceIndex, IvfFlatParams, IvfPqParams,
                                     ivf_flat_build, ivf_flat_search, ivf_pq_build,
-                                    ivf_pq_search)
+                                    ivf_pq_search, refine)
     from raft_amd.random import RngState, make_blobs
 
     n, d, nq, k, n_probes = args.rows, args.dim, args.queries, args.k, args.n_probes
@@ -75,14 +83,27 @@ def main():
 
     calls = {"ivf_pq": lambda: ivf_pq_search(pq, q, k, n_probes),
              "ivf_flat": lambda: ivf_flat_search(flat, q, k, n_probes)}
+    alone, same_ids = {}, {}
+    for r in args.refine_ratio:
+        calls[f"ivf_pq_refine_x{r}"] = lambda r=r: ivf_pq_search(pq, q, k, n_probes, dataset=x,
+                                                                 refine_ratio=r)
+        cand = ivf_pq_search(pq, q, k * r, n_probes)[1]
+        for engine in ("kernel", "torch"):
+            alone[f"refine_{engine}_x{r}"] = lambda c=cand, e=engine: refine(x, q, c, k,
+                                                                            engine=e)
+        a, b = alone[f"refine_kernel_x{r}"](), alone[f"refine_torch_x{r}"]()
+        # the engines add in different orders: near ties may swap
+        same_ids[r] = round(float((a[1] == b[1]).float().mean()), 6)
     bf_ids = BruteForceIndex(x).search(q, k)[1]
     out = {"metric": "IVF-PQ vs IVF-Flat, queries per second", "data": "blobs", "rows": n,
            "dim": d, "queries": nq, "n_lists": args.n_lists, "n_probes": n_probes, "k": k,
-           "reps": args.reps, "rounds": args.rounds,
+           "reps": args.reps, "refine_reps": args.refine_reps, "rounds": args.rounds,
            "ivf_pq": {"build_s": round(pq_s, 3), "pq_dim": pq.pq_dim, "pq_len": pq.pq_len,
                       "bytes_per_row": pq.pq_dim_pad},
            "ivf_flat": {"build_s": round(flat_s, 3), "bytes_per_row": 4 * flat.d_pad}}
-    times = {name: [] for name in calls}
+    for r in args.refine_ratio:
+        out[f"ivf_pq_refine_x{r}"] = {"n_cand": k * r, "engines_same_ids": same_ids[r]}
+    times = {name: [] for name in list(calls) + list(alone)}
     for name, f in calls.items():
         ids = f()[1]                                          # warm this shape
         hit = 0
@@ -90,13 +111,16 @@ def main():
             hit += int((ids[s:s + 1024, :, None] == bf_ids[s:s + 1024, None, :])
                        .any(dim=2).sum())
         out[name]["recall"] = round(hit / (nq * k), 4)
+    calls.update(alone)                                       # warmed above
     for _ in range(args.rounds):
         for name, f in calls.items():                         # alternate
-            t, _ = sync_time(lambda: [f() for _ in range(args.reps)])
-            times[name].append(t / args.reps)
+            reps = args.refine_reps if name in alone else args.reps
+            t, _ = sync_time(lambda: [f() for _ in range(reps)])
+            times[name].append(t / reps)
     for name, ts in times.items():
-        out[name].update(qps_median=round(nq / statistics.median(ts)),
-                         qps_min=round(nq / max(ts)), qps_max=round(nq / min(ts)))
+        out.setdefault(name, {}).update(
+            qps_median=round(nq / statistics.median(ts)), qps_min=round(nq / max(ts)),
+            qps_max=round(nq / min(ts)), ms_median=round(1e3 * statistics.median(ts), 3))
     print(json.dumps(out), flush=True)
 
 

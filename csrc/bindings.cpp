@@ -142,6 +142,10 @@ void launch_ivf_pq_scan(const unsigned char*, const long long*, const long long*
                         const long long*, const unsigned int*, long long, float*, long long,
                         long long, long long, long long, int, int, int, int, int, int,
                         hipStream_t);
+// from refine.hip
+int refine_key_slots(int);
+void launch_refine(const void*, int, long long, long long, const float*, const long long*,
+                   float*, long long*, long long, int, int, int, int, hipStream_t);
 // from gemm_rocblas.cpp
 void gemm_bf16_f32_rowmajor(const void*, const void*, float*, long long, long long,
                             long long, float, void*);
@@ -1111,6 +1115,49 @@ void ivf_pq_scan(torch::Tensor codes, torch::Tensor list_offsets, torch::Tensor 
       (int)d, pq_dim, pq_len, (int)metric, (int)y_split, cur_stream());
 }
 
+// refine: the k best of every query's candidate rows by exact fp32 distance.
+// dataset [n, d] fp32 / bf16 / fp16 with any row stride; k is dists.size(1).
+void refine_topk(torch::Tensor dataset, torch::Tensor queries, torch::Tensor candidates,
+                 torch::Tensor dists, torch::Tensor ids, int64_t metric) {
+  TORCH_CHECK(dataset.is_cuda() && queries.is_cuda() && candidates.is_cuda() &&
+              dists.is_cuda() && ids.is_cuda() && queries.device() == dataset.device() &&
+              candidates.device() == dataset.device() && dists.device() == dataset.device() &&
+              ids.device() == dataset.device(),
+              "refine_topk: all tensors must be on one GPU");
+  int dtype = -1;
+  if (dataset.scalar_type() == torch::kFloat32) dtype = 0;
+  else if (dataset.scalar_type() == torch::kBFloat16) dtype = 1;
+  else if (dataset.scalar_type() == torch::kFloat16) dtype = 2;
+  TORCH_CHECK(dtype >= 0 && dataset.dim() == 2 && dataset.size(1) >= 1 &&
+              (dataset.size(1) == 1 || dataset.stride(1) == 1) && dataset.stride(0) >= 0,
+              "refine_topk: dataset must be fp32, bf16 or fp16 [n, d] with stride(1) == 1");
+  const long long n = dataset.size(0), d = dataset.size(1);
+  TORCH_CHECK(n < 4294967295ll, "refine_topk: the data set must have fewer than 2^32 - 1 rows");
+  TORCH_CHECK(queries.is_contiguous() && queries.dim() == 2 &&
+              queries.scalar_type() == torch::kFloat32 && queries.size(1) == d,
+              "refine_topk: queries must be contiguous fp32 [q, ", d, "]");
+  const long long nq = queries.size(0);
+  TORCH_CHECK(candidates.is_contiguous() && candidates.dim() == 2 &&
+              candidates.scalar_type() == torch::kInt64 && candidates.size(0) == nq,
+              "refine_topk: candidates must be contiguous int64 [q, n_cand]");
+  const long long n_cand = candidates.size(1);
+  TORCH_CHECK(dists.dim() == 2 && dists.size(0) == nq && dists.size(1) >= 1 &&
+              dists.is_contiguous() && dists.scalar_type() == torch::kFloat32 &&
+              ids.dim() == 2 && ids.size(0) == nq && ids.size(1) == dists.size(1) &&
+              ids.is_contiguous() && ids.scalar_type() == torch::kInt64,
+              "refine_topk: dists must be contiguous fp32 [q, k], ids contiguous int64 [q, k]");
+  const long long k = dists.size(1);
+  TORCH_CHECK(d <= 8192 && n_cand >= 1 && n_cand <= 4096 &&
+              k <= raft_amd::refine_key_slots((int)n_cand) && nq <= 2147483647ll,
+              "refine_topk: serves d <= 8192, 1 <= n_cand <= 4096 and k <= n_cand rounded "
+              "up to a power of two (at least 256)");
+  raft_amd::launch_refine(
+      dataset.data_ptr(), dtype, n, n > 1 ? dataset.stride(0) : 0, queries.data_ptr<float>(),
+      reinterpret_cast<const long long*>(candidates.data_ptr<int64_t>()),
+      dists.data_ptr<float>(), reinterpret_cast<long long*>(ids.data_ptr<int64_t>()), nq,
+      (int)d, (int)n_cand, (int)k, (int)metric, cur_stream());
+}
+
 void bitmap_row_degrees(torch::Tensor bitmap, torch::Tensor deg) {
   const unsigned int* bm = bitmap_words(bitmap, "bitmap_row_degrees");
   TORCH_CHECK(deg.is_cuda() && deg.scalar_type() == torch::kInt64 &&
@@ -1550,6 +1597,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("probes"), pybind11::arg("pair_out_off"),
         pybind11::arg("filter_words"), pybind11::arg("filter_bits"), pybind11::arg("out"),
         pybind11::arg("metric"), pybind11::arg("y_split"));
+  m.def("refine_topk", &refine_topk,
+        "exact re-rank of kNN candidates: gather, fp32 distance and top-k in one kernel",
+        pybind11::arg("dataset"), pybind11::arg("queries"), pybind11::arg("candidates"),
+        pybind11::arg("dists"), pybind11::arg("ids"), pybind11::arg("metric"));
   m.def("bitmap_row_degrees", &bitmap_row_degrees,
         "per-row popcount of a row-padded bitmap into an int64 vector");
   m.def("bitmap_rows_to_csr", &bitmap_rows_to_csr,

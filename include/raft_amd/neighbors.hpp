@@ -148,4 +148,21 @@ void launch_ivf_pq_scan(const unsigned char* codes, const long long* list_offset
                         long long n_queries, int n_probes, int d, int pq_dim, int pq_len,
                         int metric, int y_split, hipStream_t s);
 
+// refine (csrc/refine.hip): exact re-rank of kNN candidates, one block per
+// query. dataset is [n][d] of dtype 0 fp32, 1 bf16 or 2 fp16 with rows
+// row_pitch ELEMENTS apart (n < 2^32 - 1); queries fp32 [n_queries][d];
+// candidates int64 [n_queries][n_cand]; an id outside [0, n) is no candidate
+// and is never dereferenced. dists / ids [n_queries][k] get the k best by
+// the exact fp32 distance (metric as in launch_ivf_flat_scan), best first,
+// ties to the smaller id, a repeated id repeatedly; a NaN distance becomes
+// +inf (-inf for inner product) and keeps its id; missing slots hold that
+// value and id -1. Serves d <= 8192, n_cand <= 4096 and
+// k <= refine_key_slots(n_cand) (n_cand rounded up to a power of two, at least
+// 256), else the launcher throws.
+int refine_key_slots(int n_cand);
+void launch_refine(const void* dataset, int dtype, long long n, long long row_pitch,
+                   const float* queries, const long long* candidates, float* dists,
+                   long long* ids, long long n_queries, int d, int n_cand, int k, int metric,
+                   hipStream_t s);
+
 }  // namespace raft_amd

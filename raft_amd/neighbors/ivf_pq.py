@@ -10,8 +10,9 @@ subspace's codebook. A row costs pq_dim bytes instead of 4 * d, and a search
 scores it with pq_dim table look-ups instead of d FMAs.
 
 Distances are ASYMMETRIC (ADC): from the exact query to the RECONSTRUCTED row
-centroid + decoded residual, not to the original vector. Re-ranking the
-returned candidates against the original vectors is left to the caller.
+centroid + decoded residual, not to the original vector. ivf_pq_search(...,
+dataset=x, refine_ratio=r) re-ranks k * r such candidates against the original
+vectors with neighbors.refine and returns exact distances.
 
 Storage is the IVF-Flat layout (neighbors/ivf_flat.py) with uint8 elements:
 16 codes per 16-byte chunk, pq_dim_pad = pq_dim rounded up to 16 with zero pad
@@ -362,18 +363,24 @@ def _scan_torch(index, q32, probes, pair_off, cand, fdense, bad):
 
 def ivf_pq_search(index: IvfPqIndex, queries: torch.Tensor, k: int, n_probes: int = 20, *,
                   filter=None, return_probes: bool = False,
-                  probes: torch.Tensor | None = None, res=None):
+                  probes: torch.Tensor | None = None, res=None,
+                  dataset: torch.Tensor | None = None, refine_ratio: int = 2):
     """k nearest indexed rows among the n_probes best lists of every query
     (reference ivf_pq::search).
 
     Returns (dists [q, k] fp32, ids [q, k] int64), best first, plus the probed
     lists [q, n_probes] int64 with return_probes=True. The distances are the
     asymmetric (ADC) distances from the query to the RECONSTRUCTED rows
-    (IvfPqIndex.reconstruct_list), not to the original vectors; re-ranking
-    candidates against the originals is left to the caller (search with a
-    larger k, then rank those ids exactly). InnerProduct returns the LARGEST
-    products. Missing slots hold +inf (-inf for InnerProduct) and id -1.
-    n_probes is clamped to n_lists.
+    (IvfPqIndex.reconstruct_list), not to the original vectors. InnerProduct
+    returns the LARGEST products. Missing slots hold +inf (-inf for
+    InnerProduct) and id -1. n_probes is clamped to n_lists.
+
+    dataset= [n, d] (fp32, bf16 or fp16; dataset[id] must be the vector that
+    was indexed under id) re-ranks: the search runs with k * refine_ratio
+    (refine_ratio >= 1), its ids, -1 slots included, go through
+    refine(dataset, queries, ids, k, index.metric), and the call returns the
+    EXACT distances to the original rows. With dataset=None refine_ratio is
+    ignored and nothing changes.
 
     filter, probes, the coarse step and the query chunking (candidate buffer
     within half of res.workspace_budget(), results bitwise identical for any
@@ -384,6 +391,15 @@ def ivf_pq_search(index: IvfPqIndex, queries: torch.Tensor, k: int, n_probes: in
     k = int(k)
     if k <= 0:
         raise ValueError(f"k must be positive, got {k}")
+    if dataset is not None:
+        from .refine import refine
+        refine_ratio = int(refine_ratio)
+        if refine_ratio < 1:
+            raise ValueError(f"refine_ratio must be at least 1, got {refine_ratio}")
+        out = ivf_pq_search(index, queries, k * refine_ratio, n_probes, filter=filter,
+                            return_probes=True, probes=probes, res=res)
+        dists, ids = refine(dataset, queries, out[1], k, index.metric)
+        return (dists, ids, out[2]) if return_probes else (dists, ids)
     if queries.dim() != 2 or queries.shape[1] != index.dim:
         raise ValueError(f"queries must be [q, {index.dim}], got {tuple(queries.shape)}")
     if queries.device != index.device:
