@@ -95,6 +95,16 @@ void launch_kmeans_update_verify(const float*, const int*, const int*, const flo
                                  const float*, float*, int*, const float*,
                                  const float*, float*, float*, float*, long long,
                                  long long, int, hipStream_t, float, float);
+// from kmeans_ordered.hip
+long long kmeans_order_rows_workspace(long long, int);
+int kmeans_order_rows_max_k();
+void launch_kmeans_order_rows(const int*, const float*, const float*, const float*,
+                              const float*, float, float, long long, int, int*,
+                              unsigned*, int*, hipStream_t);
+void launch_kmeans_update_verify_ordered(const float*, const unsigned*, const int*,
+                                         const float*, float*, int*, float*, float*,
+                                         float*, long long, long long, int, bool,
+                                         hipStream_t);
 // from select_k.hip
 long long select_k_workspace_bytes(long long batch);
 void launch_select_k(const float*, float*, int*, void*, long long, long long, int,
@@ -478,6 +488,93 @@ void kmeans_update_verify(torch::Tensor x, torch::Tensor perm,
       inertia_acc.has_value() ? inertia_acc->data_ptr<float>() : nullptr,
       x.size(0), x.size(1), (int)c.size(0), cur_stream(), (float)lead,
       (float)tail);
+}
+
+// whether kmeans_order_rows serves n_rows rows and k keys (the row index
+// shares a word with a flag; the scatter keeps 4 x k counters in LDS)
+bool kmeans_order_rows_serves(int64_t n_rows, int64_t k) {
+  return n_rows >= 1 && n_rows < (1ll << 31) && k >= 1 &&
+         k <= raft_amd::kmeans_order_rows_max_k();
+}
+
+int64_t kmeans_order_rows_workspace(int64_t n_rows, int64_t k) {
+  TORCH_CHECK(kmeans_order_rows_serves(n_rows, k), "kmeans_order_rows: n_rows = ",
+              n_rows, ", k = ", k, " not served");
+  return raft_amd::kmeans_order_rows_workspace(n_rows, (int)k);
+}
+
+static void check_i32_1d(const torch::Tensor& t, int64_t numel, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == torch::kInt32 &&
+              t.numel() == numel, name, " must be a contiguous int32 GPU tensor of ",
+              numel, " elements");
+}
+
+static void check_f32_1d(const torch::Tensor& t, int64_t numel, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == torch::kFloat32 &&
+              t.numel() == numel, name, " must be a contiguous float32 GPU tensor of ",
+              numel, " elements");
+}
+
+// order holds uint32 words; torch carries them as int32 (bit 31 = sign)
+void kmeans_order_rows(torch::Tensor amin, torch::Tensor dmin, torch::Tensor dmin2,
+                       torch::Tensor xn, torch::Tensor cn_max, double lead, double tail,
+                       int64_t k, torch::Tensor offsets, torch::Tensor order,
+                       torch::Tensor workspace) {
+  const int64_t n = amin.numel();
+  TORCH_CHECK(kmeans_order_rows_serves(n, k), "kmeans_order_rows: n_rows = ", n,
+              ", k = ", k, " not served (n_rows < 2^31, k <= ",
+              raft_amd::kmeans_order_rows_max_k(), ")");
+  check_i32_1d(amin, n, "amin");
+  check_f32_1d(dmin, n, "dmin");
+  check_f32_1d(dmin2, n, "dmin2");
+  check_f32_1d(xn, n, "xn");
+  check_f32_1d(cn_max, 1, "cn_max");
+  check_i32_1d(offsets, k + 1, "offsets");
+  check_i32_1d(order, n, "order");
+  check_i32_1d(workspace, raft_amd::kmeans_order_rows_workspace(n, (int)k), "workspace");
+  raft_amd::launch_kmeans_order_rows(
+      amin.data_ptr<int>(), dmin.data_ptr<float>(), dmin2.data_ptr<float>(),
+      xn.data_ptr<float>(), cn_max.data_ptr<float>(), (float)lead, (float)tail, n,
+      (int)k, offsets.data_ptr<int>(),
+      reinterpret_cast<unsigned*>(order.data_ptr<int>()), workspace.data_ptr<int>(),
+      cur_stream());
+}
+
+void kmeans_update_verify_ordered(torch::Tensor x, torch::Tensor order,
+                                  torch::Tensor offsets, torch::Tensor c,
+                                  c10::optional<torch::Tensor> dmin,
+                                  c10::optional<torch::Tensor> amin,
+                                  torch::Tensor sums, torch::Tensor counts,
+                                  c10::optional<torch::Tensor> inertia_acc,
+                                  bool write_back) {
+  check_f32_2d(x, "x");
+  check_f32_2d(c, "c");
+  const int64_t n = x.size(0), d = x.size(1), k = c.size(0);
+  TORCH_CHECK(d <= 1024, "kmeans_update_verify_ordered: d = ", d,
+              " exceeds the 1024 columns the kernel covers");
+  TORCH_CHECK(c.size(1) == d, "c must have x's columns");
+  check_i32_1d(order, n, "order");
+  check_i32_1d(offsets, k + 1, "offsets");
+  check_f32_2d(sums, "sums");
+  TORCH_CHECK(sums.size(0) >= k && sums.size(1) == d, "sums must be [>= k, d]");
+  TORCH_CHECK(counts.is_cuda() && counts.is_contiguous() && counts.numel() >= k,
+              "counts must hold k floats");
+  TORCH_CHECK(!write_back || (dmin.has_value() && amin.has_value()),
+              "write_back needs dmin and amin");
+  if (write_back) {
+    check_f32_1d(*dmin, n, "dmin");
+    check_i32_1d(*amin, n, "amin");
+  }
+  if (inertia_acc.has_value()) check_f32_1d(*inertia_acc, 1, "inertia_acc");
+  if (n == 0) return;
+  raft_amd::launch_kmeans_update_verify_ordered(
+      x.data_ptr<float>(), reinterpret_cast<const unsigned*>(order.data_ptr<int>()),
+      offsets.data_ptr<int>(), c.data_ptr<float>(),
+      write_back ? dmin->data_ptr<float>() : nullptr,
+      write_back ? amin->data_ptr<int>() : nullptr, sums.data_ptr<float>(),
+      counts.data_ptr<float>(),
+      inertia_acc.has_value() ? inertia_acc->data_ptr<float>() : nullptr, n, d,
+      (int)k, write_back, cur_stream());
 }
 
 void kmeans_update_centroids(torch::Tensor sums, torch::Tensor counts,
@@ -1429,6 +1526,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("inertia_acc") = pybind11::none(),
         pybind11::arg("lead") = 0x1p-13, pybind11::arg("tail") = 0x1p-18,
         "fused centroid-sum accumulation + exact-fp32 verify/refine (one X pass)");
+  m.def("kmeans_order_rows_serves", &kmeans_order_rows_serves,
+        pybind11::arg("n_rows"), pybind11::arg("k"),
+        "whether kmeans_order_rows takes this many rows and keys");
+  m.def("kmeans_order_rows_workspace", &kmeans_order_rows_workspace,
+        pybind11::arg("n_rows"), pybind11::arg("k"),
+        "int32 elements of kmeans_order_rows' workspace");
+  m.def("kmeans_order_rows", &kmeans_order_rows,
+        pybind11::arg("amin"), pybind11::arg("dmin"), pybind11::arg("dmin2"),
+        pybind11::arg("xn"), pybind11::arg("cn_max"), pybind11::arg("lead"),
+        pybind11::arg("tail"), pybind11::arg("k"), pybind11::arg("offsets"),
+        pybind11::arg("order"), pybind11::arg("workspace"),
+        "stable counting sort of rows by label into caller buffers: run offsets "
+        "[k + 1] and order words (row | rescan flag << 31)");
+  m.def("kmeans_update_verify_ordered", &kmeans_update_verify_ordered,
+        pybind11::arg("x"), pybind11::arg("order"), pybind11::arg("offsets"),
+        pybind11::arg("c"), pybind11::arg("dmin"), pybind11::arg("amin"),
+        pybind11::arg("sums"), pybind11::arg("counts"),
+        pybind11::arg("inertia_acc") = pybind11::none(),
+        pybind11::arg("write_back") = true,
+        "kmeans_update_verify on kmeans_order_rows' outputs; write_back=False "
+        "leaves dmin / amin untouched");
   m.def("kmeans_update_centroids", &kmeans_update_centroids,
         "centroids = counts>0 ? sums/counts : centroids");
   m.def("select_k", &select_k, "batched top-k (radix)");

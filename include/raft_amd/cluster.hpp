@@ -33,6 +33,32 @@ void launch_kmeans_update_verify(const float* x, const int* perm,
                                  long long n_rows, long long d, int n_centroids,
                                  hipStream_t s, float lead = 0x1p-13f,
                                  float tail = 0x1p-18f);
+// the same update with the row order made natively (csrc/kmeans_ordered.hip).
+// launch_kmeans_order_rows: stable counting sort of the rows by label.
+// offsets[k + 1]: position i holds a row of key j iff offsets[j] <= i <
+// offsets[j + 1]; order[n_rows]: row index in bits 0..30, in bit 31 whether
+// the row must rescan (the decision launch_kmeans_update_verify takes from
+// dmin2 - dmin, xn, cn_max, lead, tail). Labels are clamped into [0, k).
+// Needs 1 <= n_rows < 2^31, 1 <= k <= kmeans_order_rows_max_k() and a
+// workspace of kmeans_order_rows_workspace(n_rows, k) ints; no host sync, no
+// allocation.
+long long kmeans_order_rows_workspace(long long n_rows, int k);
+int kmeans_order_rows_max_k();
+void launch_kmeans_order_rows(const int* amin, const float* dmin, const float* dmin2,
+                              const float* xn, const float* cn_max_dev, float lead,
+                              float tail, long long n_rows, int k, int* offsets,
+                              unsigned* order, int* workspace, hipStream_t s);
+// launch_kmeans_update_verify_ordered: per wave the same rows, arithmetic and
+// order as launch_kmeans_update_verify on the stable sort of the labels, the
+// X row its only gather. write_back = false stores neither dmin nor amin
+// (both may then be null); sums, counts and inertia_acc are as with true.
+void launch_kmeans_update_verify_ordered(const float* x, const unsigned* order,
+                                         const int* offsets, const float* c,
+                                         float* dmin, int* amin, float* sums,
+                                         float* counts, float* inertia_acc,
+                                         long long n_rows, long long d,
+                                         int n_centroids, bool write_back,
+                                         hipStream_t s);
 // split fp32 -> nslice bf16 slices + squared row norms in one pass
 // cn_max (optional): fused max(cn) into one device float (zeroed first)
 void launch_split_bf16_norms(const float* c, void* s0, void* s1, void* s2, float* cn,

@@ -443,8 +443,17 @@ _LAST_ADAPTIVE_NSLICE = None
 class _FastLoop:
     """Minimal-dispatch EM loop: every per-iteration stage is ONE kernel
     (centroid split+norms, fused assignment, verify/repair, keyed reduction
-    with counts, centroid update) + the rocPRIM label sort + ONE packed
+    with counts, centroid update) + the label ordering + ONE packed
     allreduce.
+
+    The verified modes order the rows natively: ext.kmeans_order_rows (a
+    stable counting sort by label that also takes each row's rescan decision)
+    feeds ext.kmeans_update_verify_ordered, which gathers only X rows and
+    writes neither dmin nor amin back (nothing here reads them again). The
+    buffers of that pair live as long as the loop. RAFT_AMD_KMEANS_ORDERED=0
+    selects the earlier torch.sort + ext.kmeans_update_verify route, which
+    also serves what the counting sort does not (2^31 rows or more, k > 4096).
+    The unverified modes keep torch.sort + reduce_rows_by_key_sorted_into.
 
     Multi-GPU (world > 1): SPLIT-BATCH overlap (VERDICT r1 item 8 /
     SURVEY §6) — local rows are split in two halves; half A's packed
@@ -495,6 +504,28 @@ class _FastLoop:
         self.overlap = (comms.get_size() > 1 and n >= 2
                         and (ov_env == "1" or (ov_env != "0" and n >= 4_000_000)))
         self._cut_row_ranges()
+        # the verified update takes its row order from ext.kmeans_order_rows
+        # where that serves the shard; RAFT_AMD_KMEANS_ORDERED=0 keeps the
+        # torch.sort + kmeans_update_verify route (A/B, and the route of shards
+        # of 2^31 rows or more and of k past the counting sort's LDS)
+        self.ordered = (os.environ.get("RAFT_AMD_KMEANS_ORDERED", "1") != "0"
+                        and self.ext.kmeans_order_rows_serves(n, self.k))
+        #: per row range (keyed by its first row's address): packed, order,
+        #: offsets, table, allocated once and reused by every iteration
+        self._work = {}
+
+    def _work_buffers(self, xh):
+        work = self._work.get(xh.data_ptr())
+        if work is None:
+            n, k, kp, d, dev = xh.shape[0], self.k, self.kp, self.d, xh.device
+            i32 = dict(dtype=torch.int32, device=dev)
+            work = self._work[xh.data_ptr()] = {
+                "packed": torch.empty(kp * d + kp + 1, dtype=torch.float32, device=dev),
+                "order": torch.empty(n, **i32),
+                "offsets": torch.empty(k + 1, **i32),
+                "table": torch.empty(self.ext.kmeans_order_rows_workspace(n, k), **i32),
+            }
+        return work
 
     def _cut_row_ranges(self):
         """(x, slices, xn) per row range: the two halves under overlap, else
@@ -525,6 +556,20 @@ class _FastLoop:
             b = 2.0 * (lead * (xnh * self.cn_max).clamp_min(0).sqrt()
                        + tail * (xnh + self.cn_max))
             self.rescan_frac = ((dmin2 - dmin) < b).float().mean()
+        if self.verify and self.ordered:
+            # native row ordering (stable counting sort by label, the rescan
+            # decision folded into the order word while dmin / dmin2 / xn
+            # stream past), then the update reads that one stream plus the X
+            # rows. Nothing below reads dmin or amin again: no write-back.
+            work = self._work_buffers(xh)
+            packed = work["packed"].zero_()
+            ext.kmeans_order_rows(amin, dmin, dmin2, xnh, self.cn_max, lead, tail, k,
+                                  work["offsets"], work["order"], work["table"])
+            ext.kmeans_update_verify_ordered(
+                xh, work["order"], work["offsets"], self.centroids[:k], None, None,
+                packed[: kp * d].view(kp, d), packed[kp * d: kp * d + kp],
+                packed[-1:], write_back=False)
+            return packed
         keys_sorted, perm = torch.sort(amin)
         packed = torch.zeros(kp * d + kp + 1, dtype=torch.float32, device=xh.device)
         sums = packed[: kp * d].view(kp, d)
