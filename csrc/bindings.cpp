@@ -152,6 +152,12 @@ void launch_ivf_pq_scan(const unsigned char*, const long long*, const long long*
                         const long long*, const unsigned int*, long long, float*, long long,
                         long long, long long, long long, int, int, int, int, int, int,
                         hipStream_t);
+// from cagra.hip
+size_t cagra_search_lds_bytes(int, int, int, int, int, int, int);
+void launch_cagra_search(const void*, int, long long, long long, const int*, int, const float*,
+                         const int*, long long, int, float*, long long*, long long, int, int, int,
+                         int, int, int, int, hipStream_t);
+void launch_cagra_prune(const int*, int*, long long, int, int, hipStream_t);
 // from refine.hip
 int refine_key_slots(int);
 void launch_refine(const void*, int, long long, long long, const float*, const long long*,
@@ -1255,6 +1261,79 @@ void refine_topk(torch::Tensor dataset, torch::Tensor queries, torch::Tensor can
       (int)d, (int)n_cand, (int)k, (int)metric, cur_stream());
 }
 
+// cagra_search: greedy graph walk, one block per query. dataset [n, d] fp32 /
+// bf16 / fp16 with any row stride; graph int32 [n, degree]; seeds int32 [1 or q, S];
+// k is dists.size(1).
+void cagra_search(torch::Tensor dataset, torch::Tensor graph, torch::Tensor queries,
+                  torch::Tensor seeds, torch::Tensor dists, torch::Tensor ids,
+                  int64_t itopk_size, int64_t search_width, int64_t max_iterations,
+                  int64_t hash_slots, int64_t metric) {
+  for (const torch::Tensor* t : {&dataset, &graph, &queries, &seeds, &dists, &ids})
+    TORCH_CHECK(t->is_cuda() && t->device() == dataset.device(),
+                "cagra_search: all tensors must be on one GPU");
+  int dtype = -1;
+  if (dataset.scalar_type() == torch::kFloat32) dtype = 0;
+  else if (dataset.scalar_type() == torch::kBFloat16) dtype = 1;
+  else if (dataset.scalar_type() == torch::kFloat16) dtype = 2;
+  TORCH_CHECK(dtype >= 0 && dataset.dim() == 2 && dataset.size(1) >= 1 &&
+              (dataset.size(1) == 1 || dataset.stride(1) == 1) && dataset.stride(0) >= 0,
+              "cagra_search: dataset must be fp32, bf16 or fp16 [n, d] with stride(1) == 1");
+  const long long n = dataset.size(0), d = dataset.size(1);
+  TORCH_CHECK(n >= 1 && n < 2147483648ll, "cagra_search: the data set must have 1 to 2^31 - 1 rows");
+  TORCH_CHECK(graph.is_contiguous() && graph.dim() == 2 && graph.scalar_type() == torch::kInt32 &&
+              graph.size(0) == n && graph.size(1) >= 1,
+              "cagra_search: graph must be contiguous int32 [n, graph_degree]");
+  const long long degree = graph.size(1);
+  TORCH_CHECK(queries.is_contiguous() && queries.dim() == 2 &&
+              queries.scalar_type() == torch::kFloat32 && queries.size(1) == d,
+              "cagra_search: queries must be contiguous fp32 [q, ", d, "]");
+  const long long nq = queries.size(0);
+  TORCH_CHECK(seeds.is_contiguous() && seeds.dim() == 2 && seeds.scalar_type() == torch::kInt32 &&
+              (seeds.size(0) == 1 || seeds.size(0) == nq) && seeds.size(1) >= 1 &&
+              seeds.size(1) <= 512,
+              "cagra_search: seeds must be contiguous int32 [1 or q, 1 <= S <= 512]");
+  const long long n_seeds = seeds.size(1);
+  TORCH_CHECK(dists.dim() == 2 && dists.size(0) == nq && dists.size(1) >= 1 &&
+              dists.is_contiguous() && dists.scalar_type() == torch::kFloat32 &&
+              ids.dim() == 2 && ids.size(0) == nq && ids.size(1) == dists.size(1) &&
+              ids.is_contiguous() && ids.scalar_type() == torch::kInt64,
+              "cagra_search: dists must be contiguous fp32 [q, k], ids contiguous int64 [q, k]");
+  const long long k = dists.size(1);
+  TORCH_CHECK(d <= 4096 && itopk_size >= 1 && itopk_size <= 512 && search_width >= 1 &&
+              search_width * degree <= 512 && k <= itopk_size && max_iterations >= 1 &&
+              max_iterations <= 2147483647ll && nq <= 2147483647ll && metric >= 0 && metric <= 2,
+              "cagra_search: serves d <= 4096, itopk_size <= 512, search_width * graph_degree "
+              "<= 512, k <= itopk_size and max_iterations >= 1");
+  const long long widest = std::max<long long>(search_width * degree, n_seeds);
+  TORCH_CHECK(hash_slots >= 2 * (itopk_size + widest) && hash_slots <= 8192 &&
+              (hash_slots & (hash_slots - 1)) == 0,
+              "cagra_search: hash_slots must be a power of two in [2 * (itopk_size + "
+              "max(candidates, n_seeds)), 8192]");
+  raft_amd::launch_cagra_search(
+      dataset.data_ptr(), dtype, n, n > 1 ? dataset.stride(0) : 0, graph.data_ptr<int>(),
+      (int)degree, queries.data_ptr<float>(), seeds.data_ptr<int>(),
+      seeds.size(0) == 1 ? 0 : n_seeds, (int)n_seeds, dists.data_ptr<float>(),
+      reinterpret_cast<long long*>(ids.data_ptr<int64_t>()), nq, (int)d, (int)k, (int)itopk_size,
+      (int)search_width, (int)max_iterations, (int)hash_slots, (int)metric, cur_stream());
+}
+
+// cagra_prune: the graph_degree ranks of every kNN-graph row with the fewest detours.
+void cagra_prune(torch::Tensor knn_graph, torch::Tensor pruned) {
+  TORCH_CHECK(knn_graph.is_cuda() && pruned.is_cuda() && pruned.device() == knn_graph.device(),
+              "cagra_prune: both tensors must be on one GPU");
+  TORCH_CHECK(knn_graph.is_contiguous() && knn_graph.dim() == 2 &&
+              knn_graph.scalar_type() == torch::kInt32 && pruned.is_contiguous() &&
+              pruned.dim() == 2 && pruned.scalar_type() == torch::kInt32 &&
+              pruned.size(0) == knn_graph.size(0),
+              "cagra_prune: knn_graph must be contiguous int32 [n, kd], pruned contiguous int32 "
+              "[n, graph_degree]");
+  const long long n = knn_graph.size(0), kd = knn_graph.size(1), g = pruned.size(1);
+  TORCH_CHECK(n < 2147483648ll && kd >= 1 && kd <= 256 && g >= 1 && g <= kd,
+              "cagra_prune: serves fewer than 2^31 rows and 1 <= graph_degree <= kd <= 256");
+  raft_amd::launch_cagra_prune(knn_graph.data_ptr<int>(), pruned.data_ptr<int>(), n, (int)kd,
+                               (int)g, cur_stream());
+}
+
 void bitmap_row_degrees(torch::Tensor bitmap, torch::Tensor deg) {
   const unsigned int* bm = bitmap_words(bitmap, "bitmap_row_degrees");
   TORCH_CHECK(deg.is_cuda() && deg.scalar_type() == torch::kInt64 &&
@@ -1719,6 +1798,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "exact re-rank of kNN candidates: gather, fp32 distance and top-k in one kernel",
         pybind11::arg("dataset"), pybind11::arg("queries"), pybind11::arg("candidates"),
         pybind11::arg("dists"), pybind11::arg("ids"), pybind11::arg("metric"));
+  m.def("cagra_search", &cagra_search,
+        "CAGRA greedy graph search, one block per query, list / candidates / visited table in LDS",
+        pybind11::arg("dataset"), pybind11::arg("graph"), pybind11::arg("queries"),
+        pybind11::arg("seeds"), pybind11::arg("dists"), pybind11::arg("ids"),
+        pybind11::arg("itopk_size"), pybind11::arg("search_width"),
+        pybind11::arg("max_iterations"), pybind11::arg("hash_slots"), pybind11::arg("metric"));
+  m.def("cagra_prune", &cagra_prune,
+        "CAGRA detour-count pruning of a kNN graph, one block per node",
+        pybind11::arg("knn_graph"), pybind11::arg("pruned"));
+  m.def("cagra_search_lds_bytes", [](int64_t d, int64_t vec, int64_t itopk, int64_t cand,
+                                     int64_t n_seeds, int64_t hash_slots, int64_t width) {
+    return (int64_t)raft_amd::cagra_search_lds_bytes((int)d, (int)vec, (int)itopk, (int)cand,
+                                                     (int)n_seeds, (int)hash_slots, (int)width);
+  }, "dynamic LDS bytes of one cagra_search block");
   m.def("bitmap_row_degrees", &bitmap_row_degrees,
         "per-row popcount of a row-padded bitmap into an int64 vector");
   m.def("bitmap_rows_to_csr", &bitmap_rows_to_csr,

@@ -165,4 +165,34 @@ void launch_refine(const void* dataset, int dtype, long long n, long long row_pi
                    long long* ids, long long n_queries, int d, int n_cand, int k, int metric,
                    hipStream_t s);
 
+// CAGRA (csrc/cagra.hip). launch_cagra_search: greedy graph walk, one block
+// per query. dataset as in launch_refine with n < 2^31; graph int32
+// [n][graph_degree], -1 or any id outside [0, n) is "no edge"; queries fp32
+// [n_queries][d]; seeds int32, n_seeds per query, rows seed_pitch ELEMENTS
+// apart (0 = one row for all). The list of the itopk_size best rows by
+// (distance, smaller id) is grown from the seeds by expanding the
+// search_width best unexpanded entries per round, for at most max_iterations
+// rounds; dists / ids [n_queries][k] get its first k entries, missing slots
+// +inf (-inf for inner product) and -1. hash_slots sizes the visited table: a
+// power of two in [2 * (itopk_size + max(search_width * graph_degree,
+// n_seeds)), 8192]. Serves d <= 4096, itopk_size <= 512, search_width *
+// graph_degree <= 512, n_seeds <= 512, k <= itopk_size, else the launcher
+// throws. cagra_search_lds_bytes is the dynamic LDS of one block (vec = 4 for
+// fp32 rows, 8 for bf16 / fp16).
+//
+// launch_cagra_prune: knn_graph int32 [n][kd] (rows nearest first, distinct
+// ids) -> pruned int32 [n][graph_degree], the ranks with the smallest (detour
+// count, rank) as ids, -1 for absent. Serves graph_degree <= kd <= 256.
+int cagra_search_key_slots(int itopk_size, int n_candidates, int n_seeds);
+size_t cagra_search_lds_bytes(int d, int vec, int itopk_size, int n_candidates, int n_seeds,
+                              int hash_slots, int search_width);
+void launch_cagra_search(const void* dataset, int dtype, long long n, long long row_pitch,
+                         const int* graph, int graph_degree, const float* queries,
+                         const int* seeds, long long seed_pitch, int n_seeds, float* dists,
+                         long long* ids, long long n_queries, int d, int k, int itopk_size,
+                         int search_width, int max_iterations, int hash_slots, int metric,
+                         hipStream_t s);
+void launch_cagra_prune(const int* knn_graph, int* pruned, long long n, int kd, int graph_degree,
+                        hipStream_t s);
+
 }  // namespace raft_amd
