@@ -162,6 +162,11 @@ void launch_cagra_prune(const int*, int*, long long, int, int, hipStream_t);
 int refine_key_slots(int);
 void launch_refine(const void*, int, long long, long long, const float*, const long long*,
                    float*, long long*, long long, int, int, int, int, hipStream_t);
+// from nn_descent.hip
+void launch_nn_descent_join(const void*, int, long long, long long, const float*, const int*,
+                            const int*, int*, int*, float*, long long, int, int, int, hipStream_t);
+void launch_nn_descent_merge(float*, int*, unsigned char*, long long, int, const long long*,
+                             const int*, const float*, unsigned long long*, hipStream_t);
 // from gemm_rocblas.cpp
 void gemm_bf16_f32_rowmajor(const void*, const void*, float*, long long, long long,
                             long long, float, void*);
@@ -1334,6 +1339,84 @@ void cagra_prune(torch::Tensor knn_graph, torch::Tensor pruned) {
                                (int)g, cur_stream());
 }
 
+// nn_descent_join: per node, the best partner of every sampled row among the
+// node's other sampled rows. dataset [n, d] fp32 / bf16 / fp16 with any row
+// stride; norms fp32 [n]; new_ids / old_ids int32 [m, 2 * n_samples];
+// target / cand_id int32 and cand_val fp32 [m, 6 * n_samples].
+void nn_descent_join(torch::Tensor dataset, torch::Tensor norms, torch::Tensor new_ids,
+                     torch::Tensor old_ids, torch::Tensor target, torch::Tensor cand_id,
+                     torch::Tensor cand_val, int64_t metric) {
+  for (const torch::Tensor* t : {&dataset, &norms, &new_ids, &old_ids, &target, &cand_id,
+                                 &cand_val})
+    TORCH_CHECK(t->is_cuda() && t->device() == dataset.device(),
+                "nn_descent_join: all tensors must be on one GPU");
+  int dtype = -1;
+  if (dataset.scalar_type() == torch::kFloat32) dtype = 0;
+  else if (dataset.scalar_type() == torch::kBFloat16) dtype = 1;
+  else if (dataset.scalar_type() == torch::kFloat16) dtype = 2;
+  TORCH_CHECK(dtype >= 0 && dataset.dim() == 2 && dataset.size(1) >= 1 &&
+              (dataset.size(1) == 1 || dataset.stride(1) == 1) && dataset.stride(0) >= 0,
+              "nn_descent_join: dataset must be fp32, bf16 or fp16 [n, d] with stride(1) == 1");
+  const long long n = dataset.size(0), d = dataset.size(1);
+  TORCH_CHECK(n >= 1 && n < 2147483648ll,
+              "nn_descent_join: the data set must have 1 to 2^31 - 1 rows");
+  TORCH_CHECK(norms.is_contiguous() && norms.dim() == 1 && norms.size(0) == n &&
+              norms.scalar_type() == torch::kFloat32,
+              "nn_descent_join: norms must be contiguous fp32 [n]");
+  TORCH_CHECK(new_ids.is_contiguous() && new_ids.dim() == 2 &&
+              new_ids.scalar_type() == torch::kInt32 && new_ids.size(1) >= 2 &&
+              new_ids.size(1) % 2 == 0 && old_ids.is_contiguous() &&
+              old_ids.scalar_type() == torch::kInt32 && old_ids.sizes() == new_ids.sizes(),
+              "nn_descent_join: new_ids and old_ids must be contiguous int32 [m, 2 * n_samples]");
+  const long long m = new_ids.size(0), S = new_ids.size(1) / 2;
+  TORCH_CHECK(d <= 4096 && S <= 32 && m <= 2147483647ll && metric >= 0 && metric <= 2,
+              "nn_descent_join: serves d <= 4096 and n_samples <= 32");
+  for (const torch::Tensor* t : {&target, &cand_id, &cand_val})
+    TORCH_CHECK(t->is_contiguous() && t->dim() == 2 && t->size(0) == m && t->size(1) == 6 * S,
+                "nn_descent_join: outputs must be contiguous [m, 6 * n_samples]");
+  TORCH_CHECK(target.scalar_type() == torch::kInt32 && cand_id.scalar_type() == torch::kInt32 &&
+              cand_val.scalar_type() == torch::kFloat32,
+              "nn_descent_join: target and cand_id must be int32, cand_val fp32");
+  raft_amd::launch_nn_descent_join(
+      dataset.data_ptr(), dtype, n, n > 1 ? dataset.stride(0) : 0, norms.data_ptr<float>(),
+      new_ids.data_ptr<int>(), old_ids.data_ptr<int>(), target.data_ptr<int>(),
+      cand_id.data_ptr<int>(), cand_val.data_ptr<float>(), m, (int)d, (int)S, (int)metric,
+      cur_stream());
+}
+
+// nn_descent_merge: every target's list (vals fp32, ids int32, flags bool, all
+// [n, k]) takes in the candidates of its segment [seg_off[u], seg_off[u + 1]) of
+// cand_id / cand_val; counter int64 [1] gains the change in new-flagged entries.
+void nn_descent_merge(torch::Tensor vals, torch::Tensor ids, torch::Tensor flags,
+                      torch::Tensor seg_off, torch::Tensor cand_id, torch::Tensor cand_val,
+                      torch::Tensor counter) {
+  for (const torch::Tensor* t : {&vals, &ids, &flags, &seg_off, &cand_id, &cand_val, &counter})
+    TORCH_CHECK(t->is_cuda() && t->device() == vals.device() && t->is_contiguous(),
+                "nn_descent_merge: all tensors must be contiguous on one GPU");
+  TORCH_CHECK(vals.dim() == 2 && vals.scalar_type() == torch::kFloat32 &&
+              ids.scalar_type() == torch::kInt32 && flags.scalar_type() == torch::kBool &&
+              ids.sizes() == vals.sizes() && flags.sizes() == vals.sizes(),
+              "nn_descent_merge: vals fp32, ids int32 and flags bool must be [n, k]");
+  const long long n = vals.size(0), k = vals.size(1);
+  TORCH_CHECK(n < 2147483648ll && k >= 1 && k <= 256,
+              "nn_descent_merge: serves fewer than 2^31 rows and 1 <= k <= 256");
+  TORCH_CHECK(seg_off.dim() == 1 && seg_off.size(0) == n + 1 &&
+              seg_off.scalar_type() == torch::kInt64,
+              "nn_descent_merge: seg_off must be int64 [n + 1]");
+  TORCH_CHECK(cand_id.dim() == 1 && cand_id.scalar_type() == torch::kInt32 &&
+              cand_val.dim() == 1 && cand_val.scalar_type() == torch::kFloat32 &&
+              cand_val.size(0) == cand_id.size(0),
+              "nn_descent_merge: cand_id int32 and cand_val fp32 must be [t]");
+  TORCH_CHECK(counter.numel() == 1 && counter.scalar_type() == torch::kInt64,
+              "nn_descent_merge: counter must be int64 [1]");
+  raft_amd::launch_nn_descent_merge(
+      vals.data_ptr<float>(), ids.data_ptr<int>(),
+      reinterpret_cast<unsigned char*>(flags.data_ptr<bool>()), n, (int)k,
+      reinterpret_cast<const long long*>(seg_off.data_ptr<int64_t>()), cand_id.data_ptr<int>(),
+      cand_val.data_ptr<float>(),
+      reinterpret_cast<unsigned long long*>(counter.data_ptr<int64_t>()), cur_stream());
+}
+
 void bitmap_row_degrees(torch::Tensor bitmap, torch::Tensor deg) {
   const unsigned int* bm = bitmap_words(bitmap, "bitmap_row_degrees");
   TORCH_CHECK(deg.is_cuda() && deg.scalar_type() == torch::kInt64 &&
@@ -1812,6 +1895,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return (int64_t)raft_amd::cagra_search_lds_bytes((int)d, (int)vec, (int)itopk, (int)cand,
                                                      (int)n_seeds, (int)hash_slots, (int)width);
   }, "dynamic LDS bytes of one cagra_search block");
+  m.def("nn_descent_join", &nn_descent_join,
+        "NN-descent local join: per node a 64 x 128 MFMA tile over gathered sample rows",
+        pybind11::arg("dataset"), pybind11::arg("norms"), pybind11::arg("new_ids"),
+        pybind11::arg("old_ids"), pybind11::arg("target"), pybind11::arg("cand_id"),
+        pybind11::arg("cand_val"), pybind11::arg("metric"));
+  m.def("nn_descent_merge", &nn_descent_merge,
+        "NN-descent list merge: one block per target, dedupe and bitonic sort in LDS",
+        pybind11::arg("vals"), pybind11::arg("ids"), pybind11::arg("flags"),
+        pybind11::arg("seg_off"), pybind11::arg("cand_id"), pybind11::arg("cand_val"),
+        pybind11::arg("counter"));
   m.def("bitmap_row_degrees", &bitmap_row_degrees,
         "per-row popcount of a row-padded bitmap into an int64 vector");
   m.def("bitmap_rows_to_csr", &bitmap_rows_to_csr,

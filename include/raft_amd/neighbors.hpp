@@ -195,4 +195,26 @@ void launch_cagra_search(const void* dataset, int dtype, long long n, long long 
 void launch_cagra_prune(const int* knn_graph, int* pruned, long long n, int kd, int graph_degree,
                         hipStream_t s);
 
+// NN-descent (csrc/nn_descent.hip). launch_nn_descent_join: one block per node
+// gathers the rows of new_ids / old_ids int32 [n_nodes][2 * n_samples] (-1 or
+// any id outside [0, n) is no row) from dataset (as in launch_refine, n < 2^31),
+// forms the 64 x 128 tile of values (norms[u] + norms[v]) - 2 dot (-dot for
+// metric 2) on the bf16 matrix cores and writes, at fixed positions
+// [n_nodes][6 * n_samples], (target u, id v, value) of the smallest (value, v):
+// every NEW row among NEW, every NEW row among OLD, every OLD row among NEW; -1
+// and +inf where there is none. Serves d <= 4096, n_samples <= 32.
+//
+// launch_nn_descent_merge: one block per target u merges the candidates
+// cand_id / cand_val [seg_off[u], seg_off[u + 1]) into the list vals / ids /
+// flags [n][k] (ascending (value, id), -1 absent): distinct ids, an id already
+// listed keeps its entry and flag, a new one is flagged, u itself never enters.
+// counter gains (new flags after - before). Serves k <= 256.
+void launch_nn_descent_join(const void* dataset, int dtype, long long n, long long row_pitch,
+                            const float* norms, const int* new_ids, const int* old_ids,
+                            int* out_target, int* out_id, float* out_val, long long n_nodes, int d,
+                            int n_samples, int metric, hipStream_t s);
+void launch_nn_descent_merge(float* vals, int* ids, unsigned char* flags, long long n, int k,
+                             const long long* seg_off, const int* cand_id, const float* cand_val,
+                             unsigned long long* counter, hipStream_t s);
+
 }  // namespace raft_amd

@@ -9,6 +9,7 @@ from .ivf_pq import (IvfPqParams, IvfPqIndex, ivf_pq_build, ivf_pq_extend, ivf_p
 from .refine import refine
 from .cagra import (CagraParams, CagraIndex, cagra_build, cagra_optimize, cagra_search,
                     search_kernel_serves, optimize_kernel_serves)
+from .nn_descent import nn_descent, nn_descent_kernel_serves
 
 __all__ = ["fused_l2nn", "fused_l2nn_argmin", "knn", "BruteForceIndex",
            "brute_force_build", "eps_neighbors_l2sq", "eps_neighbors_l2sq_csr",
@@ -17,4 +18,4 @@ __all__ = ["fused_l2nn", "fused_l2nn_argmin", "knn", "BruteForceIndex",
            "ivf_flat_load", "IvfPqParams", "IvfPqIndex", "ivf_pq_build", "ivf_pq_extend",
            "ivf_pq_search", "ivf_pq_save", "ivf_pq_load", "refine", "CagraParams", "CagraIndex",
            "cagra_build", "cagra_optimize", "cagra_search", "search_kernel_serves",
-           "optimize_kernel_serves"]
+           "optimize_kernel_serves", "nn_descent", "nn_descent_kernel_serves"]

@@ -259,8 +259,13 @@ def _knn_graph(x, kd, algo, metric, seed):
     return out
 
 
-def cagra_build(dataset: torch.Tensor, params: CagraParams | None = None) -> CagraIndex:
+def cagra_build(dataset: torch.Tensor, params: CagraParams | None = None, *,
+                knn_graph: torch.Tensor | None = None) -> CagraIndex:
     """Build the graph index of dataset [n, d] (reference cagra::build).
+
+    knn_graph, an int32 or int64 [n, kd] graph as cagra_optimize takes it with
+    kd >= graph_degree (the ids of neighbors.nn_descent, say), replaces the kNN
+    search and the own-id drop described next; build_algo is not read then.
 
     A kNN graph of degree kd = min(intermediate_graph_degree, n - 1) is
     searched with k = kd + 1: build_algo "brute_force" is knn(x, x, k) in row
@@ -288,15 +293,23 @@ def cagra_build(dataset: torch.Tensor, params: CagraParams | None = None) -> Cag
     dev = dataset.device
     if dev.type == "cuda":
         require_ext()
-    kd = min(int(params.intermediate_graph_degree), n - 1)
-    algo = params.build_algo
-    if algo == "auto":
-        algo = "brute_force" if n <= _AUTO_BRUTE_FORCE_ROWS else "ivf_pq"
-    nbrs = _knn_graph(dataset, kd, algo, metric, params.seed)               # [n, kd + 1]
-    # drop the own id where it appears, else the last entry; -1 stays
-    own = nbrs == torch.arange(n, device=dev).unsqueeze(1)
-    own[:, kd] |= ~own.any(dim=1)
-    knn_graph = nbrs[~own].reshape(n, kd)
+    if knn_graph is not None:
+        if (knn_graph.dim() != 2 or knn_graph.dtype not in (torch.int32, torch.int64)
+                or knn_graph.shape[0] != n or knn_graph.shape[1] < params.graph_degree
+                or knn_graph.device != dev):
+            raise ValueError(f"knn_graph must be int32 or int64 [{n}, kd >= graph_degree] on "
+                             f"the device of the dataset")
+        kd = knn_graph.shape[1]
+    else:
+        kd = min(int(params.intermediate_graph_degree), n - 1)
+        algo = params.build_algo
+        if algo == "auto":
+            algo = "brute_force" if n <= _AUTO_BRUTE_FORCE_ROWS else "ivf_pq"
+        nbrs = _knn_graph(dataset, kd, algo, metric, params.seed)           # [n, kd + 1]
+        # drop the own id where it appears, else the last entry; -1 stays
+        own = nbrs == torch.arange(n, device=dev).unsqueeze(1)
+        own[:, kd] |= ~own.any(dim=1)
+        knn_graph = nbrs[~own].reshape(n, kd)
     graph = cagra_optimize(knn_graph, min(int(params.graph_degree), kd))
     gen = torch.Generator().manual_seed(int(params.seed))
     seeds = torch.randperm(n, generator=gen)[:min(n, _MAX_SEEDS)].int().to(dev)
