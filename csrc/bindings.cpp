@@ -136,13 +136,20 @@ void launch_masked_l2nn_verify_repair(const float*, const float*, const float*,
                                       unsigned long long*, unsigned long long*,
                                       long long, int, int, float, float, hipStream_t);
 // from ivf_flat_scan.hip
-int ivf_flat_scan_max_qg(int);
+int ivf_flat_scan_max_qg(int, int = 4);
 void launch_ivf_flat_scan(const void*, bool, const long long*, const long long*,
                           const float*, const long long*, const long long*,
                           const long long*, const long long*, const long long*,
                           const long long*, const unsigned int*, long long, float*,
                           long long, long long, long long, long long, long long,
                           long long, int, int, int, int, hipStream_t);
+// from ivf_flat_scan_i8.hip
+void launch_ivf_flat_scan_i8(const void*, bool, const long long*, const long long*,
+                             const void*, const long long*, const long long*,
+                             const long long*, const long long*, const long long*,
+                             const long long*, const unsigned int*, long long, float*,
+                             long long, long long, long long, long long, long long,
+                             long long, int, int, int, int, hipStream_t);
 // from ivf_pq.hip
 void launch_ivf_pq_encode(const float*, const long long*, const float*, const float*,
                           unsigned char*, long long, long long, int, int, int, hipStream_t);
@@ -1076,16 +1083,21 @@ void ivf_flat_scan(torch::Tensor data, torch::Tensor list_offsets, torch::Tensor
                    torch::Tensor pair_out_off, c10::optional<torch::Tensor> filter_words,
                    int64_t filter_bits, torch::Tensor out, int64_t metric, int64_t qg,
                    int64_t y_split) {
+  const auto dt = data.scalar_type();
+  const bool bf16 = dt == torch::kBFloat16;
+  const bool i8 = dt == torch::kInt8 || dt == torch::kUInt8;
   TORCH_CHECK(data.is_cuda() && data.is_contiguous() && data.dim() == 1 &&
-              (data.scalar_type() == torch::kFloat32 ||
-               data.scalar_type() == torch::kBFloat16),
-              "ivf_flat_scan: data must be a flat contiguous fp32 or bf16 GPU tensor");
-  const bool bf16 = data.scalar_type() == torch::kBFloat16;
+              (dt == torch::kFloat32 || bf16 || i8),
+              "ivf_flat_scan: data must be a flat contiguous fp32, bf16, int8 or uint8 "
+              "GPU tensor");
+  // integer rows take integer queries of their own dtype (exact dot4 scan)
   TORCH_CHECK(queries.is_cuda() && queries.is_contiguous() && queries.dim() == 2 &&
-              queries.scalar_type() == torch::kFloat32 && queries.size(1) >= 1,
-              "ivf_flat_scan: queries must be contiguous fp32 [q, d]");
+              queries.scalar_type() == (i8 ? dt : torch::kFloat32) &&
+              queries.size(1) >= 1,
+              "ivf_flat_scan: queries must be contiguous [q, d], fp32 for fp32 / bf16 "
+              "data and of the data's dtype for int8 / uint8 data");
   const long long d = queries.size(1);
-  const long long v = bf16 ? 8 : 4;
+  const long long v = i8 ? 16 : bf16 ? 8 : 4;
   const long long d_pad = (d + v - 1) / v * v;
   TORCH_CHECK(d_pad <= 4096, "ivf_flat_scan: d_pad must be <= 4096");
   const long long total_rows = indices.numel();
@@ -1115,8 +1127,16 @@ void ivf_flat_scan(torch::Tensor data, torch::Tensor list_offsets, torch::Tensor
                 "ivf_flat_scan: filter must be int32 words covering filter_bits");
     fw = reinterpret_cast<const unsigned int*>(f.data_ptr<int>());
   }
-  TORCH_CHECK(qg >= 1 && qg <= raft_amd::ivf_flat_scan_max_qg((int)d_pad),
+  TORCH_CHECK(qg >= 1 && qg <= raft_amd::ivf_flat_scan_max_qg((int)d_pad, i8 ? 1 : 4),
               "ivf_flat_scan: qg too large for d_pad");
+  if (i8) {
+    raft_amd::launch_ivf_flat_scan_i8(
+        data.data_ptr(), dt == torch::kInt8, lo, idx, queries.data_ptr(), il, ib, ic, ni,
+        pq, po, fw, filter_bits, out.data_ptr<float>(), out.numel(), n_lists, total_rows,
+        queries.size(0), n_pairs, max_items, (int)d, (int)metric, (int)qg, (int)y_split,
+        cur_stream());
+    return;
+  }
   raft_amd::launch_ivf_flat_scan(
       data.data_ptr(), bf16, lo, idx, queries.data_ptr<float>(), il, ib, ic, ni, pq, po,
       fw, filter_bits, out.data_ptr<float>(), out.numel(), n_lists, total_rows,
@@ -1863,9 +1883,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("pair_out_off"), pybind11::arg("filter_words"),
         pybind11::arg("filter_bits"), pybind11::arg("out"), pybind11::arg("metric"),
         pybind11::arg("qg"), pybind11::arg("y_split"));
-  m.def("ivf_flat_scan_max_qg", [](int64_t d_pad) {
-    return (int64_t)raft_amd::ivf_flat_scan_max_qg((int)d_pad);
-  }, "largest query-group size whose staged queries fit the scan kernel's LDS");
+  m.def("ivf_flat_scan_max_qg", [](int64_t d_pad, int64_t elem_size) {
+    TORCH_CHECK(elem_size == 1 || elem_size == 4,
+                "ivf_flat_scan_max_qg: elem_size must be 4 (fp32 / bf16 index) or 1 "
+                "(int8 / uint8 index)");
+    return (int64_t)raft_amd::ivf_flat_scan_max_qg((int)d_pad, (int)elem_size);
+  }, "largest query-group size whose staged queries fit the scan kernel's LDS",
+        pybind11::arg("d_pad"), pybind11::arg("elem_size") = 4);
   m.def("ivf_pq_encode", &ivf_pq_encode,
         "IVF-PQ: nearest codebook entry per subspace of x - centroids[labels]",
         pybind11::arg("x"), pybind11::arg("labels"), pybind11::arg("centroids"),

@@ -203,10 +203,13 @@ static void ivf_flat_scan_launch(
   HIP_CHECK(hipGetLastError());
 }
 
-int ivf_flat_scan_max_qg(int d_pad) {
+// elem_size 4: the queries staged as fp32 (fp32 and bf16 indices); 1: as bytes
+// plus one int norm per query (int8 / uint8 indices, ivf_flat_scan_i8.hip)
+int ivf_flat_scan_max_qg(int d_pad, int elem_size) {
+  const long long per_query = elem_size == 1 ? (long long)d_pad + (long long)sizeof(int)
+                                             : (long long)d_pad * (long long)sizeof(float);
   int qg = 32;
-  while (qg > 1 && (long long)qg * d_pad * (long long)sizeof(float) > IVF_SCAN_LDS_BYTES)
-    qg >>= 1;
+  while (qg > 1 && qg * per_query > IVF_SCAN_LDS_BYTES) qg >>= 1;
   return qg;
 }
 
@@ -227,7 +230,7 @@ void launch_ivf_flat_scan(const void* data, bool data_bf16,
   const int d_pad = (d + v - 1) / v * v;
   if (qg != 4 && qg != 8 && qg != 16 && qg != 32)
     throw std::runtime_error("ivf_flat_scan: qg must be 4, 8, 16 or 32");
-  if (qg > ivf_flat_scan_max_qg(d_pad))
+  if (qg > ivf_flat_scan_max_qg(d_pad, 4))
     throw std::runtime_error("ivf_flat_scan: qg * d_pad * 4 must fit 64 KiB of LDS");
   if (metric < 0 || metric > 2)
     throw std::runtime_error("ivf_flat_scan: metric must be 0 (L2), 1 (L2 sqrt) or 2 (IP)");

@@ -106,7 +106,9 @@ void launch_masked_l2nn_verify_repair(const float* x, const float* y, const floa
 // (-inf for inner product). metric: 0 squared L2 (unexpanded sum), 1 its
 // square root, 2 inner product. qg in {4, 8, 16, 32} with
 // qg <= ivf_flat_scan_max_qg(d_pad); y_split blocks share a list's groups.
-int ivf_flat_scan_max_qg(int d_pad);
+// elem_size is the bytes one staged query element takes in LDS: 4 for this
+// launcher, 1 (plus one int norm per query) for launch_ivf_flat_scan_i8.
+int ivf_flat_scan_max_qg(int d_pad, int elem_size = 4);
 void launch_ivf_flat_scan(const void* data, bool data_bf16,
                           const long long* list_offsets, const long long* indices,
                           const float* queries, const long long* item_list,
@@ -118,6 +120,24 @@ void launch_ivf_flat_scan(const void* data, bool data_bf16,
                           long long total_rows, long long n_queries, long long n_pairs,
                           long long max_items, int d, int metric, int qg, int y_split,
                           hipStream_t s);
+// The same scan over int8 (data_signed) or uint8 rows
+// (csrc/ivf_flat_scan_i8.hip): 16 one-byte elements per chunk, queries
+// [n_queries, d] bytes of the rows' type, d <= 4096. Distances are exact
+// integers (8-bit dot4 into int32) converted to fp32 once; metric 1 is the
+// fp64 root of the exact squared distance rounded to fp32. qg in
+// {4, 8, 16, 32} with qg <= ivf_flat_scan_max_qg(d_pad, 1). Every other
+// argument as in launch_ivf_flat_scan.
+void launch_ivf_flat_scan_i8(const void* data, bool data_signed,
+                             const long long* list_offsets, const long long* indices,
+                             const void* queries, const long long* item_list,
+                             const long long* item_pair_begin,
+                             const long long* item_pair_count, const long long* n_items,
+                             const long long* pair_query, const long long* pair_out_off,
+                             const unsigned int* filter_words, long long filter_bits,
+                             float* out, long long out_numel, long long n_lists,
+                             long long total_rows, long long n_queries, long long n_pairs,
+                             long long max_items, int d, int metric, int qg, int y_split,
+                             hipStream_t s);
 
 // IVF-PQ (csrc/ivf_pq.hip), 8-bit codes. codebooks is fp32
 // [pq_dim][pq_len][256] (entry-minor), pq_len = ceil(d / pq_dim), features

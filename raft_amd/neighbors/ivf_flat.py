@@ -7,8 +7,9 @@ the n_probes best lists of every query and selects the k best rows among them.
 
 Storage is ONE layout on CPU and GPU. Rows are sorted by list, every list is
 padded to a multiple of 64 rows (the wave width) and rows are interleaved in
-groups of 64: with V = 16 bytes of elements (4 fp32, 8 bf16) and d_pad = d
-rounded up to V with zeros, element (group g, chunk j, row r, v) lives at
+groups of 64: with V = 16 bytes of elements (4 fp32, 8 bf16, 16 int8 / uint8)
+and d_pad = d rounded up to V with zeros, element (group g, chunk j, row r, v)
+lives at
 
     ((g * (d_pad / V) + j) * 64 + r) * V + v
 
@@ -26,6 +27,15 @@ query: its padded probed lists in probe order) taken from the Resources
 workspace, and the generic ragged-row select engine picks the k best. The
 buffer is sized from n_probes * the longest padded list, so a query chunk
 needs no host sync.
+
+int8 / uint8 indices (csrc/ivf_flat_scan_i8.hip) keep one byte per feature and
+take queries of the same dtype. Their scan kernel has the same decomposition
+but stages the queries as packed bytes and accumulates with the 8-bit dot4
+instruction into int32, so a distance is the EXACT integer (squared L2 as
+|x|^2 + |q|^2 - 2 x.q, the row norm computed in the same pass), converted to
+fp32 once; euclidean is the fp64 root of that integer rounded to fp32. The
+torch path computes the same values in int64, so CPU and GPU agree bit for bit.
+Training and assignment run on widened fp32 values, a chunk of rows at a time.
 
 CPU tensors, and GPU indices with d_pad > 4096 or fp32_mode="native", run the
 same algorithm with plain torch ops over unpack_list (on the GPU the select
@@ -50,11 +60,17 @@ _GROUP = 64
 #: metric -> code of ext.ivf_flat_scan
 _METRIC_CODES = {DistanceType.L2Expanded: 0, DistanceType.L2SqrtExpanded: 1,
                  DistanceType.InnerProduct: 2}
-_DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1}
+_DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1, torch.int8: 2, torch.uint8: 3}
+_INT_DTYPES = (torch.int8, torch.uint8)
 #: queries one block stages: 8 measured faster than 4, 16 and 32
 #: (docs/performance.md, "IVF-Flat"); the LDS tier ext.ivf_flat_scan_max_qg
 #: lowers it for wide rows
 _DEFAULT_QG = 8
+#: the same for int8 / uint8 indices: 16 measured faster than 4, 8 and 32
+#: (docs/performance.md, "IVF-Flat, int8 / uint8")
+_DEFAULT_QG_INT = 16
+#: rows widened to fp32 at a time when integer vectors are assigned to lists
+_ASSIGN_ROWS = 1 << 20
 _QG_CHOICES = (4, 8, 16, 32)
 #: widest padded row the scan kernel stages; wider indices take the torch path
 _MAX_KERNEL_D_PAD = 4096
@@ -98,7 +114,7 @@ class IvfFlatParams:
 class IvfFlatIndex:
     """The index: centroids [n_lists, d] fp32, list_offsets int64 [n_lists+1]
     in rows (multiples of 64), list_sizes int64 [n_lists] (true sizes), data
-    (the flat interleaved buffer, fp32 or bf16), indices int64 [padded rows]
+    (the flat interleaved buffer, fp32, bf16, int8 or uint8), indices int64 [padded rows]
     (dataset ids, -1 in pad slots), metric, dim, n_rows."""
 
     def __init__(self, centroids, list_offsets, list_sizes, data, indices, metric,
@@ -185,12 +201,16 @@ def _pack(rows, ids, labels, n_lists, dim):
     return offsets, sizes, data, indices
 
 
-def _check_vectors(x, what):
+def _check_vectors(x, what, allow_int=False):
+    """x as the index stores it. allow_int admits int8 / uint8 rows (IVF-Flat
+    only; IVF-PQ shares this check and keeps rejecting them)."""
+    if allow_int and x.dim() == 2 and x.dtype in _INT_DTYPES:
+        return x
     if x.dim() != 2 or not x.dtype.is_floating_point:
         raise ValueError(f"{what} must be a 2-D floating-point tensor [rows, features]")
     if x.dtype == torch.float16:
         x = x.float()   # exact widening, as everywhere else
-    if x.dtype not in _DTYPE_CODES:
+    if x.dtype not in (torch.float32, torch.bfloat16):
         raise ValueError(f"{what} must be fp32, bf16 or fp16, got {x.dtype}")
     return x
 
@@ -199,8 +219,10 @@ def ivf_flat_build(x: torch.Tensor, params: IvfFlatParams | None = None, *,
                    centroids: torch.Tensor | None = None, res=None) -> IvfFlatIndex:
     """Build an IVF-Flat index over x [n, d] (reference ivf_flat::build).
 
-    x is fp32 or bf16 (fp16 is widened to fp32, which is exact); centroids and
-    returned distances are fp32. The centroids come from kmeans_balanced_fit
+    x is fp32, bf16, int8 or uint8 (fp16 is widened to fp32, which is exact);
+    centroids and returned distances are fp32. Integer rows are stored as they
+    are and widened to fp32 only for training (the sampled rows) and for the
+    assignment (2^20 rows at a time). The centroids come from kmeans_balanced_fit
     on a params.kmeans_trainset_fraction sample with params.seed, always with
     plain L2 (also for InnerProduct); rows are assigned with kmeans_predict.
     centroids= [n_lists, d] skips the training (an index built elsewhere, or
@@ -210,7 +232,7 @@ def ivf_flat_build(x: torch.Tensor, params: IvfFlatParams | None = None, *,
     from raft_amd.cluster.kmeans import kmeans_balanced_fit
     params = params if params is not None else IvfFlatParams()
     metric = _resolve_metric(params.metric)
-    x = _check_vectors(x, "x")
+    x = _check_vectors(x, "x", allow_int=True)
     n, d = x.shape
     if d < 1:
         raise ValueError("x needs at least one feature")
@@ -218,9 +240,18 @@ def ivf_flat_build(x: torch.Tensor, params: IvfFlatParams | None = None, *,
         n_lists = int(params.n_lists)
         if n_lists < 1 or n_lists > n:
             raise ValueError(f"n_lists must be in [1, {n}], got {n_lists}")
-        model = kmeans_balanced_fit(x.float(), n_lists, max_iter=params.kmeans_n_iters,
-                                    seed=params.seed,
-                                    sample_fraction=params.kmeans_trainset_fraction,
+        train, fraction = x, params.kmeans_trainset_fraction
+        if x.dtype in _INT_DTYPES:
+            # draw the rows kmeans_balanced_fit would draw and widen only those:
+            # the fp32 copy of the whole integer data set never exists
+            from raft_amd.random.rng import RngState, sample_without_replacement
+            n_sample = max(n_lists * 4, int(n * fraction))
+            if n_sample < n:
+                train = x[sample_without_replacement(
+                    n, n_sample, state=RngState(seed=params.seed), device=x.device)]
+            fraction = 1.0
+        model = kmeans_balanced_fit(train.float(), n_lists, max_iter=params.kmeans_n_iters,
+                                    seed=params.seed, sample_fraction=fraction,
                                     fp32_mode=params.fp32_mode)
         centroids = model.centroids
     elif centroids.dim() != 2 or centroids.shape[1] != d or centroids.shape[0] < 1:
@@ -245,7 +276,7 @@ def ivf_flat_extend(index: IvfFlatIndex, new_vectors: torch.Tensor,
     with kmeans_predict, appended to their lists and the whole buffer is
     repacked. new_indices defaults to arange(n_rows, n_rows + m)."""
     from raft_amd.cluster.kmeans import kmeans_predict
-    new_vectors = _check_vectors(new_vectors, "new_vectors")
+    new_vectors = _check_vectors(new_vectors, "new_vectors", allow_int=True)
     if new_vectors.shape[1] != index.dim:
         raise ValueError(f"new_vectors has {new_vectors.shape[1]} features, the index "
                          f"has {index.dim}")
@@ -261,7 +292,14 @@ def ivf_flat_extend(index: IvfFlatIndex, new_vectors: torch.Tensor,
     elif new_indices.dim() != 1 or new_indices.shape[0] != m:
         raise ValueError(f"new_indices must be an integer tensor [{m}]")
     new_indices = new_indices.to(dev, torch.int64)
-    if m:
+    if m and new_vectors.dtype in _INT_DTYPES:
+        # widened a chunk at a time; a row's nearest centroid does not depend on
+        # which other rows share its chunk
+        labels = torch.cat([
+            kmeans_predict(index.centroids, new_vectors[s0:s1].float(),
+                           fp32_mode=index.fp32_mode).to(torch.int64)
+            for s0, s1 in row_chunks(m, _ASSIGN_ROWS)])
+    elif m:
         labels = kmeans_predict(index.centroids, new_vectors.float(),
                                 fp32_mode=index.fp32_mode).to(torch.int64)
     else:
@@ -305,7 +343,8 @@ def _chunk_layout(index, probes):
 
 
 def _scan_kernel(index, q32, probes, pair_off, cand, fwords, fbits, qg):
-    """List-major scan of one query chunk on the GPU (no host sync)."""
+    """List-major scan of one query chunk on the GPU (no host sync). q32 is
+    fp32, or the index's dtype for an int8 / uint8 index."""
     ext = require_ext()
     dev = q32.device
     qc, n_probes = probes.shape
@@ -341,7 +380,8 @@ def _scan_torch(index, q32, probes, pair_off, cand, fdense, bad):
         size = rows.shape[0]
         if size == 0:
             continue
-        x = rows.float()
+        exact = rows.dtype in _INT_DTYPES   # int64 arithmetic, rounded to fp32 once
+        x = rows.long() if exact else rows.float()
         ok = None
         if fdense is not None:
             ok = (ids < fdense.numel()) & fdense[ids.clamp(max=fdense.numel() - 1)]
@@ -350,13 +390,18 @@ def _scan_torch(index, q32, probes, pair_off, cand, fdense, bad):
         sub = max(1, (1 << 22) // (size * index.dim))
         for s0, s1 in row_chunks(qi.numel(), sub):
             qv = q32[qi[s0:s1]]
+            if exact:
+                qv = qv.long()
             if ip:
                 dist = (x.unsqueeze(0) * qv.unsqueeze(1)).sum(dim=2)
             else:
                 diff = x.unsqueeze(0) - qv.unsqueeze(1)
                 dist = (diff * diff).sum(dim=2)
                 if index.metric == DistanceType.L2SqrtExpanded:
-                    dist = dist.sqrt()
+                    # integer rows: the fp64 root of the exact value, rounded once
+                    dist = dist.double().sqrt() if exact else dist.sqrt()
+            if exact:
+                dist = dist.float()
             if ok is not None:
                 dist = torch.where(ok.unsqueeze(0), dist, torch.full_like(dist, bad))
             cand[pair_off[qi[s0:s1], pi[s0:s1]].unsqueeze(1) + cols] = dist
@@ -417,7 +462,14 @@ def ivf_flat_search(index: IvfFlatIndex, queries: torch.Tensor, k: int,
     row whose bit is clear is never returned.
     probes: int64 [q, n_probes] lists to scan instead of the coarse step.
     qg: queries one scan block stages (4, 8, 16 or 32; default 8, lowered to
-    what 64 KiB of LDS holds: at most 16 at d = 1024, 8 at 2048, 4 at 4096).
+    what 64 KiB of LDS holds: at most 16 at d = 1024, 8 at 2048, 4 at 4096;
+    for an int8 / uint8 index the default is 16 and the LDS tiers are 32 up to
+    d = 1024, 16 at 2048, 8 at 4096).
+
+    An int8 / uint8 index takes queries of its own dtype (anything else
+    raises ValueError) and returns exact distances: the integer squared L2 or
+    inner product converted to fp32 once, for euclidean the fp64 root of the
+    integer rounded to fp32; the same bits on CPU and GPU.
 
     The coarse step is pairwise_distance(queries, centroids) in the index
     metric and the index's fp32_mode, then select_k. Queries are taken in
@@ -434,9 +486,15 @@ def ivf_flat_search(index: IvfFlatIndex, queries: torch.Tensor, k: int,
         raise ValueError(f"queries must be [q, {index.dim}], got {tuple(queries.shape)}")
     if queries.device != index.device:
         raise ValueError("queries must be on the device of the index")
+    integer = index.dtype in _INT_DTYPES
+    if integer and queries.dtype != index.dtype:
+        raise ValueError(f"an {index.dtype} index takes queries of its own dtype, got "
+                         f"{queries.dtype}")
     dev = index.device
     ext = require_ext() if dev.type == "cuda" else None
     q32 = queries.float().contiguous()
+    #: what the scan reads: integer rows meet the integer queries themselves
+    qscan = queries.contiguous() if integer else q32
     q = q32.shape[0]
     ip = index.metric == DistanceType.InnerProduct
     select_min = not ip
@@ -469,10 +527,10 @@ def ivf_flat_search(index: IvfFlatIndex, queries: torch.Tensor, k: int,
     use_kernel = (dev.type == "cuda" and index.d_pad <= _MAX_KERNEL_D_PAD
                   and index.fp32_mode != "native")
     if use_kernel:
-        qg = _DEFAULT_QG if qg is None else int(qg)
+        qg = (_DEFAULT_QG_INT if integer else _DEFAULT_QG) if qg is None else int(qg)
         if qg not in _QG_CHOICES:
             raise ValueError(f"qg must be one of {_QG_CHOICES}, got {qg}")
-        qg = min(qg, ext.ivf_flat_scan_max_qg(index.d_pad))
+        qg = min(qg, ext.ivf_flat_scan_max_qg(index.d_pad, 1 if integer else 4))
         if fdense is not None:
             fwords = Bitset.from_dense(fdense).words.contiguous()
     elif fwords is not None:
@@ -488,9 +546,9 @@ def ivf_flat_search(index: IvfFlatIndex, queries: torch.Tensor, k: int,
             cand = ws.view(((s1 - s0) * n_probes * index.max_list_pad,), torch.float32)
             row_off, pair_off = _chunk_layout(index, pc)
             if use_kernel:
-                _scan_kernel(index, q32[s0:s1], pc, pair_off, cand, fwords, fbits, qg)
+                _scan_kernel(index, qscan[s0:s1], pc, pair_off, cand, fwords, fbits, qg)
             else:
-                _scan_torch(index, q32[s0:s1], pc, pair_off, cand, fdense, bad)
+                _scan_torch(index, qscan[s0:s1], pc, pair_off, cand, fdense, bad)
             vals, pos = _select(cand, row_off, k, select_min, bad)
             dists[s0:s1], ids[s0:s1] = _finish(index, vals, pos, pc, row_off, pair_off,
                                                select_min, bad)
@@ -503,7 +561,8 @@ def ivf_flat_save(index: IvfFlatIndex, path: str) -> None:
     """Write the index to one file (reference ivf_flat::serialize): a header
     (magic, version, metric, dim, n_rows, dtype, n_lists, fp32_mode), then
     centroids, list_offsets, list_sizes, data and indices as .npy records.
-    bf16 data is stored as its 16-bit patterns."""
+    bf16 data is stored as its 16-bit patterns, int8 / uint8 data (dtype codes
+    2 and 3) as its own bytes."""
     data = index.data
     if data.dtype == torch.bfloat16:
         data = data.view(torch.int16)
@@ -536,5 +595,7 @@ def ivf_flat_load(path: str, device=None) -> IvfFlatIndex:
         raise ValueError(f"{path}: corrupt IVF-Flat header")
     if dtypes[dtype] == torch.bfloat16:
         data = data.view(torch.bfloat16)
+    elif data.dtype != dtypes[dtype]:
+        raise ValueError(f"{path}: corrupt IVF-Flat header")
     return IvfFlatIndex(centroids, offsets, sizes, data, indices, metrics[metric], dim,
                         n_rows, mode.rstrip(b"\x00").decode("ascii"))
