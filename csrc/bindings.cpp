@@ -150,6 +150,13 @@ void launch_ivf_flat_scan_i8(const void*, bool, const long long*, const long lon
                              const long long*, const unsigned int*, long long, float*,
                              long long, long long, long long, long long, long long,
                              long long, int, int, int, int, hipStream_t);
+// from pairwise_i8.hip
+void launch_row_stats_i8(const void*, bool, int*, int*, long long, int, hipStream_t);
+void launch_pairwise_i8(const void*, const void*, bool, const int*, const int*, const int*,
+                        const int*, float*, long long, long long, int, int, int, hipStream_t);
+void launch_pairwise_i8_filter(const void*, const void*, bool, const int*, const int*,
+                               const int*, float*, int*, int*, int, long long, long long,
+                               long long, int, hipStream_t);
 // from ivf_pq.hip
 void launch_ivf_pq_encode(const float*, const long long*, const float*, const float*,
                           unsigned char*, long long, long long, int, int, int, hipStream_t);
@@ -871,6 +878,87 @@ void pairwise_l2_filter(std::vector<torch::Tensor> x_slices,
                                       out_d.data_ptr<float>(), out_i.data_ptr<int>(),
                                       cnt.data_ptr<int>(), cap, col_offset, c.m, c.n,
                                       (int)c.d, c.nslice, cur_stream());
+}
+
+// ---- int8 / uint8 rows on the integer MFMA (pairwise_i8.hip) --------------
+
+// contiguous int8 / uint8 [rows, d_pad] GPU rows with d_pad a multiple of 128
+// in the kernels' range and a 16-byte aligned base
+static void check_i8_rows(const char* who, const char* what, const torch::Tensor& t) {
+  TORCH_CHECK(t.is_cuda() &&
+              (t.scalar_type() == torch::kInt8 || t.scalar_type() == torch::kUInt8) &&
+              t.dim() == 2 && t.is_contiguous() && t.size(0) >= 1,
+              who, ": ", what, " must be a contiguous, non-empty int8 or uint8 [rows, d_pad] "
+              "GPU tensor");
+  TORCH_CHECK(t.size(1) >= 128 && t.size(1) % 128 == 0 && t.size(1) <= 4096, who, ": ", what,
+              " needs d_pad a multiple of 128 and <= 4096, got ", t.size(1));
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, who, ": ", what,
+              " must be 16-byte aligned");
+}
+
+// x and y rows of one dtype and one d_pad; true for int8
+static bool check_i8_pair(const char* who, const torch::Tensor& x, const torch::Tensor& y) {
+  check_i8_rows(who, "x", x);
+  check_i8_rows(who, "y", y);
+  TORCH_CHECK(x.scalar_type() == y.scalar_type() && x.size(1) == y.size(1) &&
+              x.device() == y.device(), who, ": x and y must share dtype, d_pad and device");
+  return x.scalar_type() == torch::kInt8;
+}
+
+// a contiguous int32 tensor of these sizes on x's device
+static int* checked_i32(const char* who, const char* what, const torch::Tensor& t,
+                        at::IntArrayRef sizes, const torch::Tensor& x) {
+  TORCH_CHECK(t.device() == x.device() && t.scalar_type() == torch::kInt32 &&
+              t.is_contiguous() && t.sizes() == sizes, who, ": ", what,
+              " must be a contiguous int32 tensor of sizes ", sizes, " on x's device");
+  return t.data_ptr<int>();
+}
+
+// int32 [2, rows]: row 0 the sums of squares, row 1 the sums (uint8 shifted by -128)
+torch::Tensor row_stats_i8(torch::Tensor x) {
+  check_i8_rows("row_stats_i8", "x", x);
+  auto stat = torch::empty({2, x.size(0)}, x.options().dtype(torch::kInt32));
+  raft_amd::launch_row_stats_i8(x.data_ptr(), x.scalar_type() == torch::kInt8,
+                                stat.data_ptr<int>(), stat.data_ptr<int>() + x.size(0),
+                                x.size(0), (int)x.size(1), cur_stream());
+  return stat;
+}
+
+torch::Tensor pairwise_i8(torch::Tensor x, torch::Tensor y, torch::Tensor xstat,
+                          torch::Tensor ystat, int64_t metric_code, int64_t d_real) {
+  const bool is_signed = check_i8_pair("pairwise_i8", x, y);
+  const long long m = x.size(0), n = y.size(0);
+  const int* xs = checked_i32("pairwise_i8", "xstat", xstat, {2, m}, x);
+  const int* ys = checked_i32("pairwise_i8", "ystat", ystat, {2, n}, x);
+  TORCH_CHECK(metric_code >= 0 && metric_code <= 2,
+              "pairwise_i8: metric_code must be 0 (L2), 1 (L2 sqrt) or 2 (inner product)");
+  TORCH_CHECK(d_real >= 1 && d_real <= x.size(1), "pairwise_i8: d_real must be in [1, d_pad]");
+  auto out = torch::empty({m, n}, x.options().dtype(torch::kFloat32));
+  raft_amd::launch_pairwise_i8(x.data_ptr(), y.data_ptr(), is_signed, xs, xs + m, ys, ys + n,
+                               out.data_ptr<float>(), m, n, (int)x.size(1), (int)d_real,
+                               (int)metric_code, cur_stream());
+  return out;
+}
+
+void pairwise_i8_filter(torch::Tensor x, torch::Tensor y, torch::Tensor xn, torch::Tensor yn,
+                        torch::Tensor thr, torch::Tensor out_d, torch::Tensor out_i,
+                        torch::Tensor cnt, int64_t col_offset) {
+  const char* who = "pairwise_i8_filter";
+  const bool is_signed = check_i8_pair(who, x, y);
+  const long long m = x.size(0), n = y.size(0);
+  TORCH_CHECK(out_d.device() == x.device() && out_d.dim() == 2 && out_d.size(0) == m &&
+              out_d.size(1) >= 1 && out_d.size(1) <= std::numeric_limits<int>::max(),
+              who, ": out_d must be [m, cap] on x's device with cap in [1, 2^31)");
+  const int cap = (int)out_d.size(1);
+  TORCH_CHECK(col_offset >= 0 && col_offset + n <= std::numeric_limits<int>::max(),
+              who, ": col_offset + n must fit int32");
+  const float* od = checked_f32_vec(who, "out_d", out_d, m * cap);
+  raft_amd::launch_pairwise_i8_filter(
+      x.data_ptr(), y.data_ptr(), is_signed, checked_i32(who, "xn", xn, {m}, x),
+      checked_i32(who, "yn", yn, {n}, x), checked_i32(who, "thr", thr, {m}, x),
+      const_cast<float*>(od), checked_i32(who, "out_i", out_i, {m, cap}, x),
+      checked_i32(who, "cnt", cnt, {m}, x), cap, col_offset, m, n, (int)x.size(1),
+      cur_stream());
 }
 
 const unsigned int* bitmap_words(const torch::Tensor& bm, const char* who) {
@@ -1854,6 +1942,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("yn"), pybind11::arg("thr"), pybind11::arg("out_d"),
         pybind11::arg("out_i"), pybind11::arg("cnt"), pybind11::arg("col_offset"),
         pybind11::arg("variant") = "auto");
+  m.def("row_stats_i8", &row_stats_i8,
+        "int32 [2, rows] sums of squares and sums of int8 / uint8 rows (uint8 shifted "
+        "by -128)", pybind11::arg("x"));
+  m.def("pairwise_i8", &pairwise_i8,
+        "exact int8 / uint8 pairwise distances on the integer MFMA -> fp32 [m, n]; "
+        "metric_code 0 squared L2, 1 its root, 2 inner product",
+        pybind11::arg("x"), pybind11::arg("y"), pybind11::arg("xstat"),
+        pybind11::arg("ystat"), pybind11::arg("metric_code"), pybind11::arg("d_real"));
+  m.def("pairwise_i8_filter", &pairwise_i8_filter,
+        "threshold-filtered exact int8 / uint8 squared L2 candidate emission",
+        pybind11::arg("x"), pybind11::arg("y"), pybind11::arg("xn"), pybind11::arg("yn"),
+        pybind11::arg("thr"), pybind11::arg("out_d"), pybind11::arg("out_i"),
+        pybind11::arg("cnt"), pybind11::arg("col_offset"));
   m.def("eps_neighbors_l2sq", &eps_neighbors_l2sq,
         "verified eps-neighborhood (squared L2) packed adjacency bitmap",
         pybind11::arg("x_slices"), pybind11::arg("y_slices"), pybind11::arg("xn"),

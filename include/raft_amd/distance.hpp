@@ -41,4 +41,25 @@ void launch_pairwise_l2_filter(const void** xsl, const void** csl, const float* 
                                long long m, long long n, int d, int nslice,
                                hipStream_t s);
 
+// int8 (is_signed) / uint8 rows on the 8-bit integer MFMA
+// (csrc/pairwise_i8.hip). Operands are row-major bytes [rows][d_pad],
+// d_pad % 128 == 0 and <= 4096, 16-byte aligned, pad bytes 0 (int8) or 128
+// (uint8). launch_row_stats_i8 writes every row's sum of squares and sum in
+// the domain the kernels work in (uint8 shifted by -128). metric: 0 squared
+// L2, 1 its root, 2 inner product (xsum / ysum and d_real, the unpadded d,
+// are read for uint8 inner product only). out[m][n] gets the exact integer
+// converted to fp32 once; metric 1 the fp64 root rounded to fp32.
+void launch_row_stats_i8(const void* x, bool is_signed, int* norm, int* sum, long long rows,
+                         int d_pad, hipStream_t s);
+void launch_pairwise_i8(const void* x, const void* y, bool is_signed, const int* xnorm,
+                        const int* xsum, const int* ynorm, const int* ysum, float* out,
+                        long long m, long long n, int d_pad, int d_real, int metric,
+                        hipStream_t s);
+// squared L2 <= thresh[row] (exact int32) into the per-row candidate buffers,
+// as launch_pairwise_l2_filter; col_offset + n must fit int32
+void launch_pairwise_i8_filter(const void* x, const void* y, bool is_signed, const int* xnorm,
+                               const int* ynorm, const int* thresh, float* out_d, int* out_i,
+                               int* counts, int cap, long long col_offset, long long m,
+                               long long n, int d_pad, hipStream_t s);
+
 }  // namespace raft_amd

@@ -26,7 +26,7 @@ from enum import Enum
 import torch
 
 from raft_amd._ext import require_ext
-from raft_amd.utils import on_gpu
+from raft_amd.utils import on_gpu, row_chunks
 from raft_amd.linalg.gemm import gemm_fp32_emulated
 from raft_amd.linalg.split_bf16 import (MODE_NSLICE, pad_features,
                                         split_bf16_slices)
@@ -96,6 +96,12 @@ def pairwise_distance(x: torch.Tensor, y: torch.Tensor | None = None,
     as on the bf16 L2 path. fp64 inputs on GPU keep the fp64 reference path,
     which materialises an [m, n, d] broadcast. On CPU every metric is
     evaluated in fp64 and cast to the input dtype.
+
+    int8 / uint8 inputs (both of one dtype) serve L2Expanded, L2SqrtExpanded
+    and InnerProduct and return fp32: the exact integer converted once, the
+    euclidean distance as its fp64 root rounded to fp32, the same on both
+    devices (GPU: csrc/pairwise_i8.hip, d <= 4096). Any other pairing or
+    metric raises ValueError.
     """
     if isinstance(metric, str):
         metric = _metric_from_str(metric)
@@ -103,6 +109,8 @@ def pairwise_distance(x: torch.Tensor, y: torch.Tensor | None = None,
         y = x
     assert x.dim() == 2 and y.dim() == 2 and x.shape[1] == y.shape[1]
 
+    if x.dtype in I8_ZERO_POINT or y.dtype in I8_ZERO_POINT:
+        return _pairwise_i8(x, y, metric)
     if metric in _EXpanded_L2:
         d2 = _l2_squared(x, y, fp32_mode)
         return d2.sqrt() if metric in _SQRT_TYPES else d2
@@ -143,6 +151,75 @@ def _metric_from_str(s: str) -> DistanceType:
         if m.value == s or m.name.lower() == s.lower():
             return m
     raise ValueError(f"unknown metric {s!r}")
+
+
+#: int8 / uint8 rows (csrc/pairwise_i8.hip): the byte that pads a row for the
+#: kernels, chosen so that pads add nothing to a dot product, a norm or a sum
+I8_ZERO_POINT = {torch.int8: 0, torch.uint8: 128}
+#: metric codes of ext.pairwise_i8
+_I8_CODES = {DistanceType.L2Expanded: 0, DistanceType.L2SqrtExpanded: 1,
+             DistanceType.InnerProduct: 2}
+#: widest row the integer kernels serve: every int32 intermediate stays exact
+I8_MAX_DIM = 4096
+
+
+def check_i8(x, y, metric) -> DistanceType:
+    """The metric of an int8 / uint8 call; ValueError where the pair of dtypes
+    or the metric is not served."""
+    if isinstance(metric, str):
+        metric = _metric_from_str(metric)
+    if x.dtype != y.dtype:
+        raise ValueError(f"int8 / uint8 rows need both sides of one dtype, got "
+                         f"{x.dtype} and {y.dtype}")
+    if metric not in _I8_CODES:
+        raise ValueError(f"int8 / uint8 rows serve L2Expanded, L2SqrtExpanded and "
+                         f"InnerProduct, not {metric.name}")
+    return metric
+
+
+def i8_operands(x):
+    """GPU operands of the integer kernels: the rows padded with the dtype's
+    zero point to a multiple of 128 features (x itself where it already is
+    one), and their int32 [2, rows] statistics."""
+    n, d = x.shape
+    if d > I8_MAX_DIM:
+        raise ValueError(f"int8 / uint8 rows on the GPU serve d <= {I8_MAX_DIM}, got {d}")
+    d_pad = -(-d // 128) * 128
+    if d_pad == d and x.is_contiguous() and x.data_ptr() % 16 == 0:
+        xp = x
+    else:
+        xp = torch.full((n, d_pad), I8_ZERO_POINT[x.dtype], dtype=x.dtype, device=x.device)
+        xp[:, :d] = x
+    return xp, require_ext().row_stats_i8(xp)
+
+
+def i8_from_exact(v, metric):
+    """The fp32 result of an exact integer: converted once, euclidean as the
+    fp64 root rounded to fp32."""
+    return v.double().sqrt().float() if metric == DistanceType.L2SqrtExpanded else v.float()
+
+
+def _pairwise_i8(x, y, metric):
+    """Exact int8 / uint8 distances as fp32 [m, n]: the integer MFMA kernel on
+    the GPU, int64 torch in row chunks on the CPU (which defines the result)."""
+    metric = check_i8(x, y, metric)
+    m, n, d = x.shape[0], y.shape[0], x.shape[1]
+    if m == 0 or n == 0:
+        return torch.empty((m, n), dtype=torch.float32, device=x.device)
+    if on_gpu(x, y):
+        xp, xstat = i8_operands(x)
+        yp, ystat = (xp, xstat) if y is x else i8_operands(y)
+        return require_ext().pairwise_i8(xp, yp, xstat, ystat, _I8_CODES[metric], d)
+    out = torch.empty((m, n), dtype=torch.float32, device=x.device)
+    yl = y.long()
+    yt, yn = yl.t().contiguous(), (yl * yl).sum(dim=1)
+    for r0, r1 in row_chunks(m, max(1, (1 << 24) // n)):
+        xl = x[r0:r1].long()
+        g = xl @ yt
+        if metric != DistanceType.InnerProduct:
+            g = (xl * xl).sum(dim=1, keepdim=True) + yn - 2 * g
+        out[r0:r1] = i8_from_exact(g, metric)
+    return out
 
 
 def _gemm_xyt(x, y, fp32_mode):

@@ -22,6 +22,11 @@ MI355X design — the GPU path never materializes the distance matrix:
      and mechanism as the verified kmeans L2-NN engine, csrc/kmeans.hip).
      fp32_mode="native" skips the MFMA filter entirely and runs the tiled
      fp32 rocBLAS path.
+int8 / uint8 rows (queries of the same dtype) run the same three steps over
+the integer MFMA kernels of csrc/pairwise_i8.hip: distances are exact int32,
+so the sampled threshold is used as it stands and step 4 is only the tiled
+fallback of under- / overflowed rows. Results are the exact integers converted
+to fp32 once (euclidean: the fp64 root), bit-comparable with IVF-Flat int8.
 """
 from __future__ import annotations
 
@@ -29,6 +34,8 @@ import torch
 
 from raft_amd._ext import require_ext
 from raft_amd.distance import pairwise_distance, DistanceType
+from raft_amd.distance.pairwise import (I8_ZERO_POINT, _metric_from_str, check_i8,
+                                        i8_from_exact, i8_operands)
 from raft_amd.linalg.split_bf16 import (MODE_NSLICE, SPLIT_BOUND, pad_features,
                                         row_sqnorms, split_bf16_slices)
 from raft_amd.matrix.select_k import select_k
@@ -45,6 +52,8 @@ def knn(x: torch.Tensor, queries: torch.Tensor, k: int,
     workspace budget (reference: workspace-resource-driven batching) — set a
     workspace limit via res.set_workspace_limit(nbytes) to bound scratch.
     """
+    if x.dtype in I8_ZERO_POINT or queries.dtype in I8_ZERO_POINT:
+        return _knn_i8(x, queries, k, metric, query_chunk, index_chunk, res)
     if x.dtype == torch.float16 and x.is_cuda:
         # fp16 -> fp32 is exact: ride the fp32 filtered path (reference
         # supports half-precision knn; the bf16 split of an exact widening
@@ -78,14 +87,29 @@ class BruteForceIndex:
     brute-force knn (index object holding the dataset + norms). Caches the
     bf16 filter slice(s) and the row norms of the index matrix, so repeated
     searches skip the per-call index split — at 100M x 128 fp32 the split
-    alone is a measurable fraction of a one-shot knn() call.
+    alone is a measurable fraction of a one-shot knn() call. An int8 / uint8
+    index on the GPU caches the rows padded for the integer kernels and their
+    statistics instead (metric: L2Expanded, L2SqrtExpanded or InnerProduct).
     """
 
-    def __init__(self, x: torch.Tensor, fp32_mode: str = "auto", res=None):
+    def __init__(self, x: torch.Tensor, fp32_mode: str = "auto", res=None,
+                 metric: DistanceType | str = DistanceType.L2Expanded):
         self.dim_orig = x.shape[1]
         self.fp32_mode = fp32_mode
+        self.metric = _metric_from_str(metric) if isinstance(metric, str) else metric
+        self._i8 = None
+        if x.dtype in I8_ZERO_POINT:
+            check_i8(x, x, self.metric)
+            self._filterable, self.slices, self.xn = False, None, None
+            if x.is_cuda:
+                # self.x is the unpadded view of the cached padded rows
+                self._i8 = i8_operands(x)
+                x = self._i8[0][:, :x.shape[1]]
+            self.x = x
+            return
         self._filterable = (
             x.is_cuda and x.dtype in (torch.bfloat16, torch.float32)
+            and self.metric == DistanceType.L2Expanded
             and not (x.dtype == torch.float32 and fp32_mode == "native"))
         if self._filterable:
             # pad the MFMA K granularity ONCE at build (zero columns change
@@ -109,6 +133,9 @@ class BruteForceIndex:
 
     def search(self, queries: torch.Tensor, k: int, res=None):
         """k nearest index rows per query. Returns (dists [q,k], idx [q,k])."""
+        if self.x.dtype in I8_ZERO_POINT:
+            return _knn_i8(self.x, queries, k, self.metric, None, None, res,
+                           pre=self._i8)
         if queries.shape[1] != self.x.shape[1]:
             queries = torch.nn.functional.pad(
                 queries, (0, self.x.shape[1] - queries.shape[1]))
@@ -118,13 +145,15 @@ class BruteForceIndex:
             r = get_resources(res if res is not None else queries.device)
             return _knn_gpu_filtered(self.x, queries, k, self.fp32_mode,
                                      res=r, pre=(self.slices, self.xn))
-        return knn(self.x, queries, k, fp32_mode=self.fp32_mode, res=res)
+        return knn(self.x, queries, k, metric=self.metric, fp32_mode=self.fp32_mode,
+                   res=res)
 
 
-def brute_force_build(x: torch.Tensor, fp32_mode: str = "auto",
-                      res=None) -> BruteForceIndex:
+def brute_force_build(x: torch.Tensor, fp32_mode: str = "auto", res=None,
+                      metric: DistanceType | str = DistanceType.L2Expanded
+                      ) -> BruteForceIndex:
     """reference brute_force::build parity."""
-    return BruteForceIndex(x, fp32_mode=fp32_mode, res=res)
+    return BruteForceIndex(x, fp32_mode=fp32_mode, res=res, metric=metric)
 
 
 def _tiles_from_budget(budget_bytes: int, q: int, n: int, d: int, k: int):
@@ -302,12 +331,106 @@ def _knn_gpu_filtered_block(x, queries, k, fp32_mode, index_chunk, res,
     return vals, idx
 
 
+def _knn_i8(x, queries, k, metric, query_chunk, index_chunk, res, pre=None):
+    """int8 / uint8 kNN with exact integer distances (fp32 out, as
+    pairwise_distance converts them). GPU, L2 kinds, n >= 8k: the sample ->
+    filter -> select pipeline over csrc/pairwise_i8.hip; everything else the
+    tiled path over the exact pairwise_distance. pre: (padded rows, stats) of
+    a BruteForceIndex."""
+    metric = check_i8(x, queries, metric)
+    from raft_amd.core.resources import get_resources
+    res = get_resources(res if res is not None else queries.device)
+    if (x.is_cuda and queries.is_cuda and metric != DistanceType.InnerProduct
+            and x.shape[0] >= 8 * k):
+        return _knn_i8_filtered(x, queries, k, metric, res, pre)
+    qc, ic = _tiles_from_budget(res.workspace_budget(), queries.shape[0],
+                                x.shape[0], x.shape[1], k)
+    return _knn_tiled(x, queries, k, metric, query_chunk or qc, index_chunk or ic,
+                      "auto")
+
+
+def _knn_i8_filtered(x, queries, k, metric, res, pre=None,
+                     index_chunk: int = 4_000_000):
+    """The pipeline of _knn_gpu_filtered_block on exact int32 distances: the
+    j-th smallest sampled distance is the threshold as it stands (nothing is
+    emulated, so nothing is inflated and nothing is re-ranked); rows whose
+    buffer under- or overflowed go to the tiled path."""
+    ext = require_ext()
+    m, d = queries.shape
+    n, dev = x.shape[0], queries.device
+    xp, xstat = pre if pre is not None else i8_operands(x)
+    qp, qstat = i8_operands(queries)
+    xn = xstat[0]
+
+    s = max(min(65536, n), n // 1024)
+    gen = torch.Generator(device="cpu").manual_seed(0x5eed)
+    sample_idx = torch.randint(0, n, (s,), generator=gen).to(dev)
+    xs, sstat = xp[sample_idx].contiguous(), xstat[:, sample_idx].contiguous()
+    j = min(max(2, (4 * k * s) // n), s)
+
+    cap = max(16384, 32 * k)
+    budget = max(res.workspace_budget(), 1 << 22)
+    q_block = max(256, min(m, int(budget // (2 * (cap * 8 + 64)))))
+    vals = torch.empty((m, k), dtype=torch.float32, device=dev)
+    idx = torch.empty((m, k), dtype=torch.int64, device=dev)
+    bad = torch.empty(m, dtype=torch.bool, device=dev)
+    for b0, b1 in row_chunks(m, q_block):
+        mb = b1 - b0
+        qb, qs = qp[b0:b1], qstat[:, b0:b1].contiguous()
+        thr = torch.empty(mb, dtype=torch.int32, device=dev)
+        for s0, s1 in row_chunks(mb, 8192):
+            ds = ext.pairwise_i8(qb[s0:s1], xs, qs[:, s0:s1].contiguous(), sstat, 0, d)
+            thr[s0:s1] = select_k(ds, j, select_min=True)[0][:, -1].to(torch.int32)
+        del ds
+        ws_d = res.get_workspace((mb, cap), torch.float32)
+        ws_i = res.get_workspace((mb, cap), torch.int32)
+        cand_d = ws_d.view((mb, cap), torch.float32)
+        cand_d.fill_(float("inf"))
+        cand_i = ws_i.view((mb, cap), torch.int32)
+        cand_i.fill_(-1)
+        cnt = torch.zeros(mb, dtype=torch.int32, device=dev)
+        for c0, c1 in row_chunks(n, index_chunk):
+            ext.pairwise_i8_filter(qb, xp[c0:c1], qs[0], xn[c0:c1], thr, cand_d,
+                                   cand_i, cnt, c0)
+        dv, pos = select_k(cand_d, k, select_min=True)
+        vals[b0:b1] = dv
+        idx[b0:b1] = torch.gather(cand_i, 1, pos.to(torch.int64)).to(torch.int64)
+        bad[b0:b1] = (cnt < k) | (cnt > cap)
+        ws_d.free()
+        ws_i.free()
+
+    rows = bad.nonzero(as_tuple=True)[0]
+    if rows.numel():
+        qc, ic = _tiles_from_budget(budget, rows.numel(), n, d, k)
+        bd, bi = _knn_tiled(x, queries[rows], k, DistanceType.L2Expanded, qc, ic, "auto")
+        vals[rows] = bd
+        idx[rows] = bi
+    if metric == DistanceType.L2SqrtExpanded:
+        # the root of the EXACT integer: an fp32 candidate value is one only
+        # below 2^24, which d * 255^2 stays under up to d = 258
+        sq = vals if d * 255 * 255 < (1 << 24) else _exact_sq_i8(x, queries, idx)
+        vals = i8_from_exact(sq, metric)
+    return vals, idx
+
+
+def _exact_sq_i8(x, queries, idx):
+    """int64 squared distances of the selected [q, k] pairs, recomputed."""
+    q, k = idx.shape
+    d = x.shape[1]
+    out = torch.empty((q, k), dtype=torch.int64, device=idx.device)
+    for r0, r1 in row_chunks(q, max(1, (1 << 25) // (k * d))):
+        diff = (x[idx[r0:r1].reshape(-1)].reshape(r1 - r0, k, d).long()
+                - queries[r0:r1, None, :].long())
+        out[r0:r1] = (diff * diff).sum(dim=2)
+    return out
+
+
 def _knn_tiled(x, queries, k, metric, query_chunk, index_chunk, fp32_mode):
     """Exact tiled path (distance tiles + per-tile select + k-way merge)."""
     q = queries.shape[0]
     n = x.shape[0]
-    out_dtype = torch.float32 if (queries.is_cuda and queries.dtype == torch.bfloat16) \
-        else queries.dtype
+    out_dtype = torch.float32 if ((queries.is_cuda and queries.dtype == torch.bfloat16)
+                                  or queries.dtype in I8_ZERO_POINT) else queries.dtype
     out_d = torch.empty((q, k), dtype=out_dtype, device=queries.device)
     out_i = torch.empty((q, k), dtype=torch.int64, device=queries.device)
     for qs, qe in row_chunks(q, query_chunk):
