@@ -19,8 +19,9 @@ BUILD = ROOT / "build" / "ext"
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 #: extra hipcc flags of single sources (CMakeLists.txt carries the same):
 #: ivf_pq.hip, refine.hip, cagra.hip, kmeans_ordered.hip, nn_descent.hip,
-#: ivf_flat_scan_i8.hip and pairwise_i8.hip are compiled without the packed
-#: fp32 instructions, all their fp32 arithmetic is scalar per lane
+#: ivf_flat_scan_i8.hip, pairwise_i8.hip and pairwise_bits.hip are compiled
+#: without the packed fp32 instructions, all their fp32 arithmetic is scalar
+#: per lane
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {
     "ivf_pq.hip": _NO_PACKED_FP32,
@@ -30,6 +31,7 @@ SOURCE_FLAGS = {
     "nn_descent.hip": _NO_PACKED_FP32,
     "ivf_flat_scan_i8.hip": _NO_PACKED_FP32,
     "pairwise_i8.hip": _NO_PACKED_FP32,
+    "pairwise_bits.hip": _NO_PACKED_FP32,
 }
 
 

@@ -157,6 +157,13 @@ void launch_pairwise_i8(const void*, const void*, bool, const int*, const int*, 
 void launch_pairwise_i8_filter(const void*, const void*, bool, const int*, const int*,
                                const int*, float*, int*, int*, int, long long, long long,
                                long long, int, hipStream_t);
+// from pairwise_bits.hip
+void launch_pairwise_bits(const void*, const void*, float*, long long, long long, int,
+                          hipStream_t);
+void launch_pairwise_bits_filter(const void*, const void*, const int*, float*, int*, int*, int,
+                                 long long, long long, long long, int, hipStream_t);
+void launch_pack_bits(const void*, int, unsigned char*, long long, long long, long long, float,
+                      hipStream_t);
 // from ivf_pq.hip
 void launch_ivf_pq_encode(const float*, const long long*, const float*, const float*,
                           unsigned char*, long long, long long, int, int, int, hipStream_t);
@@ -959,6 +966,72 @@ void pairwise_i8_filter(torch::Tensor x, torch::Tensor y, torch::Tensor xn, torc
       const_cast<float*>(od), checked_i32(who, "out_i", out_i, {m, cap}, x),
       checked_i32(who, "cnt", cnt, {m}, x), cap, col_offset, m, n, (int)x.size(1),
       cur_stream());
+}
+
+// ---- bit-packed rows, bitwise Hamming (pairwise_bits.hip) -------------------
+
+// contiguous uint8 [rows, nbytes_pad] GPU rows, nbytes_pad a multiple of 16 in
+// the kernels' range, rows below 2^31 and a 16-byte aligned base
+static void check_bits_rows(const char* who, const char* what, const torch::Tensor& t) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kUInt8 && t.dim() == 2 &&
+              t.is_contiguous() && t.size(0) >= 1 &&
+              t.size(0) <= std::numeric_limits<int>::max(),
+              who, ": ", what, " must be a contiguous, non-empty uint8 [rows, nbytes_pad] "
+              "GPU tensor of fewer than 2^31 rows");
+  TORCH_CHECK(t.size(1) >= 16 && t.size(1) % 16 == 0 && t.size(1) <= (1 << 21), who, ": ",
+              what, " needs nbytes_pad a multiple of 16 and <= 2^21, got ", t.size(1));
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, who, ": ", what,
+              " must be 16-byte aligned");
+}
+
+static void check_bits_pair(const char* who, const torch::Tensor& x, const torch::Tensor& y) {
+  check_bits_rows(who, "x", x);
+  check_bits_rows(who, "y", y);
+  TORCH_CHECK(x.size(1) == y.size(1) && x.device() == y.device(), who,
+              ": x and y must share nbytes_pad and device");
+}
+
+torch::Tensor pairwise_bits(torch::Tensor x, torch::Tensor y) {
+  check_bits_pair("pairwise_bits", x, y);
+  auto out = torch::empty({x.size(0), y.size(0)}, x.options().dtype(torch::kFloat32));
+  raft_amd::launch_pairwise_bits(x.data_ptr(), y.data_ptr(), out.data_ptr<float>(), x.size(0),
+                                 y.size(0), (int)x.size(1), cur_stream());
+  return out;
+}
+
+void pairwise_bits_filter(torch::Tensor x, torch::Tensor y, torch::Tensor thr,
+                          torch::Tensor out_d, torch::Tensor out_i, torch::Tensor cnt,
+                          int64_t col_offset) {
+  const char* who = "pairwise_bits_filter";
+  check_bits_pair(who, x, y);
+  const long long m = x.size(0), n = y.size(0);
+  TORCH_CHECK(out_d.device() == x.device() && out_d.dim() == 2 && out_d.size(0) == m &&
+              out_d.size(1) >= 1 && out_d.size(1) <= std::numeric_limits<int>::max(),
+              who, ": out_d must be [m, cap] on x's device with cap in [1, 2^31)");
+  const int cap = (int)out_d.size(1);
+  TORCH_CHECK(col_offset >= 0 && col_offset + n <= std::numeric_limits<int>::max(),
+              who, ": col_offset + n must fit int32");
+  const float* od = checked_f32_vec(who, "out_d", out_d, m * cap);
+  raft_amd::launch_pairwise_bits_filter(
+      x.data_ptr(), y.data_ptr(), checked_i32(who, "thr", thr, {m}, x),
+      const_cast<float*>(od), checked_i32(who, "out_i", out_i, {m, cap}, x),
+      checked_i32(who, "cnt", cnt, {m}, x), cap, col_offset, m, n, (int)x.size(1),
+      cur_stream());
+}
+
+// uint8 [n, ceil(d / 8)]: bit j % 8 of byte j / 8 is x[j] > threshold (fp32 compare)
+torch::Tensor pack_bits(torch::Tensor x, double threshold) {
+  const auto dt = x.scalar_type();
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 &&
+              (dt == torch::kFloat32 || dt == torch::kBFloat16 || dt == torch::kFloat16),
+              "pack_bits: x must be an fp32, bf16 or fp16 [n, d] GPU tensor");
+  TORCH_CHECK(x.size(1) >= 1 && (x.size(1) == 1 || x.stride(1) == 1) && x.stride(0) >= 0,
+              "pack_bits: x needs d >= 1 and unit stride along a row");
+  auto out = torch::empty({x.size(0), (x.size(1) + 7) / 8}, x.options().dtype(torch::kUInt8));
+  raft_amd::launch_pack_bits(x.data_ptr(), dt == torch::kFloat32 ? 0 : dt == torch::kBFloat16 ? 1 : 2,
+                             out.data_ptr<uint8_t>(), x.size(0), x.size(1), x.stride(0),
+                             (float)threshold, cur_stream());
+  return out;
 }
 
 const unsigned int* bitmap_words(const torch::Tensor& bm, const char* who) {
@@ -1955,6 +2028,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("x"), pybind11::arg("y"), pybind11::arg("xn"), pybind11::arg("yn"),
         pybind11::arg("thr"), pybind11::arg("out_d"), pybind11::arg("out_i"),
         pybind11::arg("cnt"), pybind11::arg("col_offset"));
+  m.def("pairwise_bits", &pairwise_bits,
+        "bitwise Hamming distances of bit-packed uint8 rows -> fp32 [m, n] counts",
+        pybind11::arg("x"), pybind11::arg("y"));
+  m.def("pairwise_bits_filter", &pairwise_bits_filter,
+        "threshold-filtered bitwise Hamming candidate emission",
+        pybind11::arg("x"), pybind11::arg("y"), pybind11::arg("thr"), pybind11::arg("out_d"),
+        pybind11::arg("out_i"), pybind11::arg("cnt"), pybind11::arg("col_offset"));
+  m.def("pack_bits", &pack_bits,
+        "pack x > threshold into uint8 [n, ceil(d / 8)], little bit order",
+        pybind11::arg("x"), pybind11::arg("threshold") = 0.0);
   m.def("eps_neighbors_l2sq", &eps_neighbors_l2sq,
         "verified eps-neighborhood (squared L2) packed adjacency bitmap",
         pybind11::arg("x_slices"), pybind11::arg("y_slices"), pybind11::arg("xn"),

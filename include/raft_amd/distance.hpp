@@ -62,4 +62,20 @@ void launch_pairwise_i8_filter(const void* x, const void* y, bool is_signed, con
                                int* counts, int cap, long long col_offset, long long m,
                                long long n, int d_pad, hipStream_t s);
 
+// Bitwise Hamming over bit-packed rows on the vector ALU (xor + popcount,
+// csrc/pairwise_bits.hip). Operands are row-major bytes [rows][nbytes_pad],
+// nbytes_pad % 16 == 0 and <= 2^21, 16-byte aligned, pad bytes 0, rows below
+// 2^31. out[m][n] gets the count of differing bits as fp32 (exact).
+void launch_pairwise_bits(const void* x, const void* y, float* out, long long m, long long n,
+                          int nbytes_pad, hipStream_t s);
+// count <= thresh[row] into the per-row candidate buffers, as
+// launch_pairwise_i8_filter; col_offset + n must fit int32
+void launch_pairwise_bits_filter(const void* x, const void* y, const int* thresh, float* out_d,
+                                 int* out_i, int* counts, int cap, long long col_offset,
+                                 long long m, long long n, int nbytes_pad, hipStream_t s);
+// out[rows][ceil(d / 8)]: bit j % 8 of byte j / 8 is x[row * ld + j] > threshold,
+// compared in fp32; dtype 0 fp32, 1 bf16, 2 fp16
+void launch_pack_bits(const void* x, int dtype, unsigned char* out, long long rows,
+                      long long d, long long ld, float threshold, hipStream_t s);
+
 }  // namespace raft_amd

@@ -1,3 +1,3 @@
-from .pairwise import pairwise_distance, DistanceType
+from .pairwise import pairwise_distance, pack_bits, DistanceType
 
-__all__ = ["pairwise_distance", "DistanceType"]
+__all__ = ["pairwise_distance", "pack_bits", "DistanceType"]

@@ -43,6 +43,7 @@ class DistanceType(Enum):
     dice            1 - 2 <x,y> / (|x|^2 + |y|^2), 0 on a zero denominator
     braycurtis      sum|x-y| / sum|x+y|, 0 on a zero denominator
     haversine       great-circle angle between [lat, lon] rows in radians
+    bitwise_hamming differing BITS of bit-packed uint8 rows (a count, not a mean)
     """
     L2Expanded = "sqeuclidean"          # squared L2 via expansion
     L2SqrtExpanded = "euclidean"        # sqrt of the above
@@ -64,6 +65,7 @@ class DistanceType(Enum):
     DiceExpanded = "dice"
     BrayCurtis = "braycurtis"
     Haversine = "haversine"
+    BitwiseHamming = "bitwise_hamming"
 
 
 _SQRT_TYPES = {DistanceType.L2SqrtExpanded, DistanceType.L2SqrtUnexpanded}
@@ -102,11 +104,18 @@ def pairwise_distance(x: torch.Tensor, y: torch.Tensor | None = None,
     euclidean distance as its fp64 root rounded to fp32, the same on both
     devices (GPU: csrc/pairwise_i8.hip, d <= 4096). Any other pairing or
     metric raises ValueError.
+
+    BitwiseHamming takes bit-packed uint8 rows [rows, nbytes] on both sides
+    (see pack_bits) and returns the number of differing bits as fp32, exact
+    for 8 * nbytes < 2^24 (wider rows raise ValueError), the same on both
+    devices (GPU: csrc/pairwise_bits.hip).
     """
     if isinstance(metric, str):
         metric = _metric_from_str(metric)
     if y is None:
         y = x
+    if metric == DistanceType.BitwiseHamming:
+        return _pairwise_bits(x, y)
     assert x.dim() == 2 and y.dim() == 2 and x.shape[1] == y.shape[1]
 
     if x.dtype in I8_ZERO_POINT or y.dtype in I8_ZERO_POINT:
@@ -220,6 +229,78 @@ def _pairwise_i8(x, y, metric):
             g = (xl * xl).sum(dim=1, keepdim=True) + yn - 2 * g
         out[r0:r1] = i8_from_exact(g, metric)
     return out
+
+
+#: bit-packed rows (csrc/pairwise_bits.hip): a count must stay below 2^24 to be
+#: exact in fp32
+BITS_MAX_BYTES = (1 << 21) - 1
+
+
+def check_bits(x, y):
+    """ValueError unless x and y are bit-packed uint8 rows of one width that
+    bitwise Hamming serves."""
+    if x.dtype != torch.uint8 or y.dtype != torch.uint8:
+        raise ValueError(f"bitwise_hamming needs bit-packed uint8 rows on both sides, got "
+                         f"{x.dtype} and {y.dtype}")
+    if x.dim() != 2 or y.dim() != 2 or x.shape[1] != y.shape[1]:
+        raise ValueError(f"bitwise_hamming needs [rows, nbytes] operands of one nbytes, got "
+                         f"{tuple(x.shape)} and {tuple(y.shape)}")
+    if x.shape[1] > BITS_MAX_BYTES:
+        raise ValueError(f"bitwise_hamming serves 8 * nbytes < 2^24, got nbytes = {x.shape[1]}")
+
+
+def bits_operands(x):
+    """GPU operand of the bit kernels: the rows zero-padded to a multiple of
+    16 bytes (x itself where it already is one, contiguous and aligned)."""
+    n, nbytes = x.shape
+    pad = -(-nbytes // 16) * 16
+    if pad == nbytes and x.is_contiguous() and x.data_ptr() % 16 == 0:
+        return x
+    xp = torch.zeros((n, pad), dtype=torch.uint8, device=x.device)
+    xp[:, :nbytes] = x
+    return xp
+
+
+_POPCOUNT = torch.tensor([bin(v).count("1") for v in range(256)], dtype=torch.uint8)
+
+
+def _pairwise_bits(x, y):
+    """Differing bits as fp32 [m, n]: the xor + popcount kernel on the GPU; on
+    the CPU (which defines the result) xor, a 256-entry popcount table and an
+    int64 sum, in row chunks."""
+    check_bits(x, y)
+    m, n, nbytes = x.shape[0], y.shape[0], x.shape[1]
+    if m == 0 or n == 0 or nbytes == 0:
+        return torch.zeros((m, n), dtype=torch.float32, device=x.device)
+    if on_gpu(x, y):
+        xp = bits_operands(x)
+        return require_ext().pairwise_bits(xp, xp if y is x else bits_operands(y))
+    out = torch.empty((m, n), dtype=torch.float32, device=x.device)
+    table = _POPCOUNT.to(x.device)
+    for r0, r1 in row_chunks(m, max(1, (1 << 24) // (n * nbytes))):
+        diff = (x[r0:r1, None, :] ^ y[None, :, :]).long()
+        out[r0:r1] = table[diff].sum(dim=2, dtype=torch.int64).float()
+    return out
+
+
+def pack_bits(x: torch.Tensor, threshold: float = 0.0) -> torch.Tensor:
+    """Bit-pack the rows of x [n, d] (fp32 / bf16 / fp16) into uint8
+    [n, ceil(d / 8)]: bit j % 8 of byte j // 8 is x[:, j] > threshold, compared
+    in fp32; the tail bits of the last byte are 0. The rows bitwise_hamming
+    takes. GPU: the ballot kernel of csrc/pairwise_bits.hip (any row stride)."""
+    if x.dim() != 2 or x.dtype not in _NATIVE_DTYPES:
+        raise ValueError(f"pack_bits needs an fp32, bf16 or fp16 [n, d] tensor, got "
+                         f"{x.dtype} {tuple(x.shape)}")
+    n, d = x.shape
+    if n == 0 or d == 0:
+        return torch.zeros((n, (d + 7) // 8), dtype=torch.uint8, device=x.device)
+    if x.is_cuda:
+        if d > 1 and x.stride(1) != 1:
+            x = x.contiguous()
+        return require_ext().pack_bits(x, float(threshold))
+    bits = torch.nn.functional.pad(x.float() > threshold, (0, -d % 8))
+    weights = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.int32)
+    return (bits.view(n, -1, 8).int() * weights).sum(dim=2).to(torch.uint8)
 
 
 def _gemm_xyt(x, y, fp32_mode):

@@ -27,6 +27,8 @@ the integer MFMA kernels of csrc/pairwise_i8.hip: distances are exact int32,
 so the sampled threshold is used as it stands and step 4 is only the tiled
 fallback of under- / overflowed rows. Results are the exact integers converted
 to fp32 once (euclidean: the fp64 root), bit-comparable with IVF-Flat int8.
+metric="bitwise_hamming" takes bit-packed uint8 rows and runs the same exact
+pipeline over the xor + popcount kernels of csrc/pairwise_bits.hip.
 """
 from __future__ import annotations
 
@@ -34,8 +36,8 @@ import torch
 
 from raft_amd._ext import require_ext
 from raft_amd.distance import pairwise_distance, DistanceType
-from raft_amd.distance.pairwise import (I8_ZERO_POINT, _metric_from_str, check_i8,
-                                        i8_from_exact, i8_operands)
+from raft_amd.distance.pairwise import (I8_ZERO_POINT, _metric_from_str, bits_operands,
+                                        check_bits, check_i8, i8_from_exact, i8_operands)
 from raft_amd.linalg.split_bf16 import (MODE_NSLICE, SPLIT_BOUND, pad_features,
                                         row_sqnorms, split_bf16_slices)
 from raft_amd.matrix.select_k import select_k
@@ -52,6 +54,9 @@ def knn(x: torch.Tensor, queries: torch.Tensor, k: int,
     workspace budget (reference: workspace-resource-driven batching) — set a
     workspace limit via res.set_workspace_limit(nbytes) to bound scratch.
     """
+    if (_metric_from_str(metric) if isinstance(metric, str)
+            else metric) == DistanceType.BitwiseHamming:
+        return _knn_bits(x, queries, k, res)
     if x.dtype in I8_ZERO_POINT or queries.dtype in I8_ZERO_POINT:
         return _knn_i8(x, queries, k, metric, query_chunk, index_chunk, res)
     if x.dtype == torch.float16 and x.is_cuda:
@@ -90,6 +95,7 @@ class BruteForceIndex:
     alone is a measurable fraction of a one-shot knn() call. An int8 / uint8
     index on the GPU caches the rows padded for the integer kernels and their
     statistics instead (metric: L2Expanded, L2SqrtExpanded or InnerProduct).
+    metric=BitwiseHamming: bit-packed uint8 rows, cached zero-padded to 16 bytes.
     """
 
     def __init__(self, x: torch.Tensor, fp32_mode: str = "auto", res=None,
@@ -97,7 +103,16 @@ class BruteForceIndex:
         self.dim_orig = x.shape[1]
         self.fp32_mode = fp32_mode
         self.metric = _metric_from_str(metric) if isinstance(metric, str) else metric
-        self._i8 = None
+        self._i8 = self._bits = None
+        if self.metric == DistanceType.BitwiseHamming:
+            check_bits(x, x)
+            self._filterable, self.slices, self.xn = False, None, None
+            if x.is_cuda:
+                # self.x is the unpadded view of the cached padded rows
+                self._bits = bits_operands(x)
+                x = self._bits[:, :x.shape[1]]
+            self.x = x
+            return
         if x.dtype in I8_ZERO_POINT:
             check_i8(x, x, self.metric)
             self._filterable, self.slices, self.xn = False, None, None
@@ -133,6 +148,8 @@ class BruteForceIndex:
 
     def search(self, queries: torch.Tensor, k: int, res=None):
         """k nearest index rows per query. Returns (dists [q,k], idx [q,k])."""
+        if self.metric == DistanceType.BitwiseHamming:
+            return _knn_bits(self.x, queries, k, res, pre=self._bits)
         if self.x.dtype in I8_ZERO_POINT:
             return _knn_i8(self.x, queries, k, self.metric, None, None, res,
                            pre=self._i8)
@@ -349,23 +366,26 @@ def _knn_i8(x, queries, k, metric, query_chunk, index_chunk, res, pre=None):
                       "auto")
 
 
-def _knn_i8_filtered(x, queries, k, metric, res, pre=None,
-                     index_chunk: int = 4_000_000):
-    """The pipeline of _knn_gpu_filtered_block on exact int32 distances: the
-    j-th smallest sampled distance is the threshold as it stands (nothing is
-    emulated, so nothing is inflated and nothing is re-ranked); rows whose
-    buffer under- or overflowed go to the tiled path."""
-    ext = require_ext()
+def _knn_exact_filtered(x, queries, k, metric, res, sampler, emit,
+                        index_chunk: int = 4_000_000):
+    """The pipeline of _knn_gpu_filtered_block on exact integer distances
+    (int8 / uint8 squared L2, bitwise Hamming): the j-th smallest sampled
+    distance is the threshold as it stands (nothing is emulated, so nothing is
+    inflated and nothing is re-ranked); rows whose buffer under- or overflowed
+    go to the tiled path over pairwise_distance(metric).
+
+    sampler(sample_idx) prepares the sampled index rows and returns
+    dists(q0, q1), the fp32 [q1 - q0, s] distances of those query rows to
+    them; emit(q0, q1, c0, c1, thr, cand_d, cand_i, cnt) runs the filter
+    kernel of query rows q0:q1 over index rows c0:c1. Returns (vals, idx, the
+    share of rows that took the tiled path)."""
     m, d = queries.shape
     n, dev = x.shape[0], queries.device
-    xp, xstat = pre if pre is not None else i8_operands(x)
-    qp, qstat = i8_operands(queries)
-    xn = xstat[0]
 
     s = max(min(65536, n), n // 1024)
     gen = torch.Generator(device="cpu").manual_seed(0x5eed)
     sample_idx = torch.randint(0, n, (s,), generator=gen).to(dev)
-    xs, sstat = xp[sample_idx].contiguous(), xstat[:, sample_idx].contiguous()
+    dists = sampler(sample_idx)
     j = min(max(2, (4 * k * s) // n), s)
 
     cap = max(16384, 32 * k)
@@ -376,10 +396,9 @@ def _knn_i8_filtered(x, queries, k, metric, res, pre=None,
     bad = torch.empty(m, dtype=torch.bool, device=dev)
     for b0, b1 in row_chunks(m, q_block):
         mb = b1 - b0
-        qb, qs = qp[b0:b1], qstat[:, b0:b1].contiguous()
         thr = torch.empty(mb, dtype=torch.int32, device=dev)
         for s0, s1 in row_chunks(mb, 8192):
-            ds = ext.pairwise_i8(qb[s0:s1], xs, qs[:, s0:s1].contiguous(), sstat, 0, d)
+            ds = dists(b0 + s0, b0 + s1)
             thr[s0:s1] = select_k(ds, j, select_min=True)[0][:, -1].to(torch.int32)
         del ds
         ws_d = res.get_workspace((mb, cap), torch.float32)
@@ -390,8 +409,7 @@ def _knn_i8_filtered(x, queries, k, metric, res, pre=None,
         cand_i.fill_(-1)
         cnt = torch.zeros(mb, dtype=torch.int32, device=dev)
         for c0, c1 in row_chunks(n, index_chunk):
-            ext.pairwise_i8_filter(qb, xp[c0:c1], qs[0], xn[c0:c1], thr, cand_d,
-                                   cand_i, cnt, c0)
+            emit(b0, b1, c0, c1, thr, cand_d, cand_i, cnt)
         dv, pos = select_k(cand_d, k, select_min=True)
         vals[b0:b1] = dv
         idx[b0:b1] = torch.gather(cand_i, 1, pos.to(torch.int64)).to(torch.int64)
@@ -402,14 +420,67 @@ def _knn_i8_filtered(x, queries, k, metric, res, pre=None,
     rows = bad.nonzero(as_tuple=True)[0]
     if rows.numel():
         qc, ic = _tiles_from_budget(budget, rows.numel(), n, d, k)
-        bd, bi = _knn_tiled(x, queries[rows], k, DistanceType.L2Expanded, qc, ic, "auto")
+        bd, bi = _knn_tiled(x, queries[rows], k, metric, qc, ic, "auto")
         vals[rows] = bd
         idx[rows] = bi
+    return vals, idx, rows.numel() / m
+
+
+def _knn_i8_filtered(x, queries, k, metric, res, pre=None):
+    """_knn_exact_filtered over csrc/pairwise_i8.hip, squared L2 throughout;
+    the root is taken of the selected values."""
+    ext = require_ext()
+    d = queries.shape[1]
+    xp, xstat = pre if pre is not None else i8_operands(x)
+    qp, qstat = i8_operands(queries)
+
+    def sampler(sample_idx):
+        xs, sstat = xp[sample_idx].contiguous(), xstat[:, sample_idx].contiguous()
+        return lambda q0, q1: ext.pairwise_i8(qp[q0:q1], xs, qstat[:, q0:q1].contiguous(),
+                                              sstat, 0, d)
+
+    def emit(q0, q1, c0, c1, thr, cand_d, cand_i, cnt):
+        ext.pairwise_i8_filter(qp[q0:q1], xp[c0:c1], qstat[0, q0:q1], xstat[0, c0:c1], thr,
+                               cand_d, cand_i, cnt, c0)
+
+    vals, idx, _ = _knn_exact_filtered(x, queries, k, DistanceType.L2Expanded, res,
+                                       sampler, emit)
     if metric == DistanceType.L2SqrtExpanded:
         # the root of the EXACT integer: an fp32 candidate value is one only
         # below 2^24, which d * 255^2 stays under up to d = 258
         sq = vals if d * 255 * 255 < (1 << 24) else _exact_sq_i8(x, queries, idx)
         vals = i8_from_exact(sq, metric)
+    return vals, idx
+
+
+def _knn_bits(x, queries, k, res, pre=None, stats=None):
+    """Bitwise Hamming kNN over bit-packed uint8 rows, exact counts as fp32.
+    GPU, n >= 8k: _knn_exact_filtered over csrc/pairwise_bits.hip; everything
+    else the tiled path over the exact pairwise_distance. pre: the padded rows
+    of a BruteForceIndex. stats (a dict) receives "tiled_share", the share of
+    query rows that the filter handed to the tiled path."""
+    check_bits(x, queries)
+    from raft_amd.core.resources import get_resources
+    res = get_resources(res if res is not None else queries.device)
+    if not (x.is_cuda and queries.is_cuda and x.shape[0] >= 8 * k):
+        qc, ic = _tiles_from_budget(res.workspace_budget(), queries.shape[0],
+                                    x.shape[0], x.shape[1], k)
+        return _knn_tiled(x, queries, k, DistanceType.BitwiseHamming, qc, ic, "auto")
+    ext = require_ext()
+    xp = pre if pre is not None else bits_operands(x)
+    qp = bits_operands(queries)
+
+    def sampler(sample_idx):
+        xs = xp[sample_idx].contiguous()
+        return lambda q0, q1: ext.pairwise_bits(qp[q0:q1], xs)
+
+    def emit(q0, q1, c0, c1, thr, cand_d, cand_i, cnt):
+        ext.pairwise_bits_filter(qp[q0:q1], xp[c0:c1], thr, cand_d, cand_i, cnt, c0)
+
+    vals, idx, share = _knn_exact_filtered(x, queries, k, DistanceType.BitwiseHamming, res,
+                                           sampler, emit)
+    if stats is not None:
+        stats["tiled_share"] = share
     return vals, idx
 
 
