@@ -41,6 +41,8 @@ def main():
     p.add_argument("--queries", type=int, default=10_000)
     p.add_argument("--n-lists", type=int, default=1024)
     p.add_argument("--pq-dim", type=int, default=0)
+    p.add_argument("--pq-bits", type=int, choices=(4, 8), default=8,
+                   help="bits of one code: 8 (csrc/ivf_pq.hip) or 4 (csrc/ivf_pq4.hip)")
     p.add_argument("--n-probes", type=int, default=32)
     p.add_argument("--k", type=int, default=10)
     p.add_argument("--refine-ratio", type=int, nargs="*", default=[1, 2, 4])
@@ -75,10 +77,10 @@ def main():
     warm = x[:max(args.n_lists * 8, n // 16)]
     ivf_flat_build(warm, IvfFlatParams(n_lists=args.n_lists))
     flat_s, flat = sync_time(lambda: ivf_flat_build(x, IvfFlatParams(n_lists=args.n_lists)))
-    pq_params = IvfPqParams(n_lists=args.n_lists, pq_dim=args.pq_dim)
+    pq_params = IvfPqParams(n_lists=args.n_lists, pq_dim=args.pq_dim, pq_bits=args.pq_bits)
     ivf_pq_build(warm, pq_params)
     pq_s, pq = sync_time(lambda: ivf_pq_build(x, pq_params))
-    print(f"# built: flat {flat_s:.2f} s, pq {pq_s:.2f} s (pq_dim {pq.pq_dim})",
+    print(f"# built: flat {flat_s:.2f} s, pq {pq_s:.2f} s (pq_dim {pq.pq_dim}, pq_bits {pq.pq_bits})",
           file=sys.stderr, flush=True)
 
     calls = {"ivf_pq": lambda: ivf_pq_search(pq, q, k, n_probes),
@@ -99,7 +101,7 @@ def main():
            "dim": d, "queries": nq, "n_lists": args.n_lists, "n_probes": n_probes, "k": k,
            "reps": args.reps, "refine_reps": args.refine_reps, "rounds": args.rounds,
            "ivf_pq": {"build_s": round(pq_s, 3), "pq_dim": pq.pq_dim, "pq_len": pq.pq_len,
-                      "bytes_per_row": pq.pq_dim_pad},
+                      "pq_bits": pq.pq_bits, "bytes_per_row": pq.row_bytes},
            "ivf_flat": {"build_s": round(flat_s, 3), "bytes_per_row": 4 * flat.d_pad}}
     for r in args.refine_ratio:
         out[f"ivf_pq_refine_x{r}"] = {"n_cand": k * r, "engines_same_ids": same_ids[r]}

@@ -18,13 +18,14 @@ CSRC = ROOT / "csrc"
 BUILD = ROOT / "build" / "ext"
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 #: extra hipcc flags of single sources (CMakeLists.txt carries the same):
-#: ivf_pq.hip, refine.hip, cagra.hip, kmeans_ordered.hip, nn_descent.hip,
+#: ivf_pq.hip, ivf_pq4.hip, refine.hip, cagra.hip, kmeans_ordered.hip, nn_descent.hip,
 #: ivf_flat_scan_i8.hip, pairwise_i8.hip and pairwise_bits.hip are compiled
 #: without the packed fp32 instructions, all their fp32 arithmetic is scalar
 #: per lane
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {
     "ivf_pq.hip": _NO_PACKED_FP32,
+    "ivf_pq4.hip": _NO_PACKED_FP32,
     "refine.hip": _NO_PACKED_FP32,
     "cagra.hip": _NO_PACKED_FP32,
     "kmeans_ordered.hip": _NO_PACKED_FP32,

@@ -179,6 +179,16 @@ void launch_cagra_search(const void*, int, long long, long long, const int*, int
                          const int*, long long, int, float*, long long*, long long, int, int, int,
                          int, int, int, int, hipStream_t);
 void launch_cagra_prune(const int*, int*, long long, int, int, hipStream_t);
+// from ivf_pq4.hip
+void launch_ivf_pq4_encode(const float*, const long long*, const float*, const float*,
+                           unsigned char*, long long, long long, int, int, int, hipStream_t);
+int ivf_pq4_scan_max_qg(int, int);
+void launch_ivf_pq4_scan(const unsigned char*, const long long*, const long long*,
+                         const float*, const float*, const float*, const long long*,
+                         const long long*, const long long*, const long long*,
+                         const long long*, const long long*, const unsigned int*, long long,
+                         float*, long long, long long, long long, long long, long long,
+                         long long, int, int, int, int, int, int, hipStream_t);
 // from refine.hip
 int refine_key_slots(int);
 void launch_refine(const void*, int, long long, long long, const float*, const long long*,
@@ -1305,20 +1315,20 @@ void ivf_flat_scan(torch::Tensor data, torch::Tensor list_offsets, torch::Tensor
       cur_stream());
 }
 
-// (pq_dim, pq_len) of codebooks [pq_dim, pq_len, 256] for rows of d features
+// (pq_dim, pq_len) of codebooks [pq_dim, pq_len, book] for rows of d features
 static std::pair<int, int> ivf_pq_shape(const torch::Tensor& centroids,
                                         const torch::Tensor& codebooks, long long d,
-                                        const char* who) {
+                                        const char* who, long long book = 256) {
   TORCH_CHECK(centroids.is_cuda() && centroids.is_contiguous() && centroids.dim() == 2 &&
               centroids.scalar_type() == torch::kFloat32 && centroids.size(0) >= 1 &&
               centroids.size(1) == d,
               who, ": centroids must be contiguous fp32 [n_lists, ", d, "]");
   TORCH_CHECK(codebooks.is_cuda() && codebooks.is_contiguous() && codebooks.dim() == 3 &&
-              codebooks.scalar_type() == torch::kFloat32 && codebooks.size(2) == 256 &&
+              codebooks.scalar_type() == torch::kFloat32 && codebooks.size(2) == book &&
               codebooks.size(0) >= 1 && codebooks.size(0) <= d &&
               codebooks.size(1) == (d + codebooks.size(0) - 1) / codebooks.size(0),
-              who, ": codebooks must be contiguous fp32 [pq_dim, ceil(d / pq_dim), 256] "
-              "with pq_dim in [1, d]");
+              who, ": codebooks must be contiguous fp32 [pq_dim, ceil(d / pq_dim), ", book,
+              "] with pq_dim in [1, d]");
   return {(int)codebooks.size(0), (int)codebooks.size(1)};
 }
 
@@ -1402,6 +1412,97 @@ void ivf_pq_scan(torch::Tensor codes, torch::Tensor list_offsets, torch::Tensor 
       centroids.data_ptr<float>(), codebooks.data_ptr<float>(), pr, po, fw, filter_bits,
       out.data_ptr<float>(), out.numel(), n_lists, total_rows, nq, (int)probes.size(1),
       (int)d, pq_dim, pq_len, (int)metric, (int)y_split, cur_stream());
+}
+
+// IVF-PQ encode with 4-bit codes: codes [n, row_bytes] uint8, two subspaces
+// per byte (the even one in bits 0..3), is written in full, pad nibbles and
+// pad bytes 0; row_bytes = ceil(pq_dim / 2) rounded up to 16.
+void ivf_pq4_encode(torch::Tensor x, torch::Tensor labels, torch::Tensor centroids,
+                    torch::Tensor codebooks, torch::Tensor codes) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2 &&
+              x.scalar_type() == torch::kFloat32 && x.size(1) >= 1,
+              "ivf_pq4_encode: x must be contiguous fp32 [n, d]");
+  const long long n = x.size(0), d = x.size(1);
+  const auto [pq_dim, pq_len] = ivf_pq_shape(centroids, codebooks, d, "ivf_pq4_encode", 16);
+  TORCH_CHECK(pq_len <= 32, "ivf_pq4_encode: pq_len must be <= 32");
+  TORCH_CHECK(labels.is_cuda() && labels.is_contiguous() &&
+              labels.scalar_type() == torch::kInt64 && labels.dim() == 1 &&
+              labels.numel() == n,
+              "ivf_pq4_encode: labels must be a contiguous int64 GPU tensor [n]");
+  const long long row_bytes = ((pq_dim + 1) / 2 + 15) / 16 * 16;
+  TORCH_CHECK(codes.is_cuda() && codes.is_contiguous() &&
+              codes.scalar_type() == torch::kUInt8 && codes.dim() == 2 &&
+              codes.size(0) == n && codes.size(1) == row_bytes &&
+              reinterpret_cast<uintptr_t>(codes.data_ptr()) % 16 == 0,
+              "ivf_pq4_encode: codes must be contiguous, 16-byte aligned uint8 [n, ",
+              row_bytes, "]");
+  raft_amd::launch_ivf_pq4_encode(
+      x.data_ptr<float>(), reinterpret_cast<const long long*>(labels.data_ptr<int64_t>()),
+      centroids.data_ptr<float>(), codebooks.data_ptr<float>(), codes.data_ptr<uint8_t>(), n,
+      centroids.size(0), (int)d, pq_dim, pq_len, cur_stream());
+}
+
+// IVF-PQ list-major LUT scan of one query chunk of a 4-bit index into the
+// ragged candidate buffer `out`: every padded row of every probed list is
+// written. The item / pair arrays are those of ivf_flat_scan.
+void ivf_pq4_scan(torch::Tensor codes, torch::Tensor list_offsets, torch::Tensor indices,
+                  torch::Tensor queries, torch::Tensor centroids, torch::Tensor codebooks,
+                  torch::Tensor item_list, torch::Tensor item_pair_begin,
+                  torch::Tensor item_pair_count, torch::Tensor n_items,
+                  torch::Tensor pair_query, torch::Tensor pair_out_off,
+                  c10::optional<torch::Tensor> filter_words, int64_t filter_bits,
+                  torch::Tensor out, int64_t metric, int64_t qg, int64_t y_split) {
+  const auto i64 = [](const torch::Tensor& t, long long numel, const char* what) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kInt64 && t.is_contiguous() &&
+                t.numel() == numel,
+                "ivf_pq4_scan: ", what, " must be a contiguous int64 GPU tensor of ", numel,
+                " elements");
+    return reinterpret_cast<const long long*>(t.data_ptr<int64_t>());
+  };
+  TORCH_CHECK(queries.is_cuda() && queries.is_contiguous() && queries.dim() == 2 &&
+              queries.scalar_type() == torch::kFloat32 && queries.size(1) >= 1,
+              "ivf_pq4_scan: queries must be contiguous fp32 [q, d]");
+  const long long d = queries.size(1);
+  const auto [pq_dim, pq_len] = ivf_pq_shape(centroids, codebooks, d, "ivf_pq4_scan", 16);
+  const int max_qg = raft_amd::ivf_pq4_scan_max_qg(pq_dim, pq_len);
+  TORCH_CHECK(max_qg >= 1, "ivf_pq4_scan: serves pq_dim <= 256 and pq_len <= 32");
+  TORCH_CHECK(qg >= 1 && qg <= max_qg, "ivf_pq4_scan: qg too large for 64 KiB of LDS");
+  const long long row_bytes = ((pq_dim + 1) / 2 + 15) / 16 * 16;
+  const long long total_rows = indices.numel();
+  TORCH_CHECK(codes.is_cuda() && codes.is_contiguous() && codes.dim() == 1 &&
+              codes.scalar_type() == torch::kUInt8 && total_rows % 64 == 0 &&
+              codes.numel() == total_rows * row_bytes &&
+              reinterpret_cast<uintptr_t>(codes.data_ptr()) % 16 == 0,
+              "ivf_pq4_scan: codes must be a flat, 16-byte aligned uint8 GPU tensor of "
+              "indices.numel() rows of row_bytes bytes, the row count a multiple of 64");
+  const long long n_lists = centroids.size(0);
+  const long long n_pairs = pair_query.numel();
+  const long long max_items = item_list.numel();
+  const long long* lo = i64(list_offsets, n_lists + 1, "list_offsets");
+  const long long* idx = i64(indices, total_rows, "indices");
+  const long long* il = i64(item_list, max_items, "item_list");
+  const long long* ib = i64(item_pair_begin, max_items, "item_pair_begin");
+  const long long* ic = i64(item_pair_count, max_items, "item_pair_count");
+  const long long* ni = i64(n_items, 1, "n_items");
+  const long long* pq = i64(pair_query, n_pairs, "pair_query");
+  const long long* po = i64(pair_out_off, n_pairs, "pair_out_off");
+  TORCH_CHECK(out.is_cuda() && out.is_contiguous() && out.dim() == 1 &&
+              out.scalar_type() == torch::kFloat32,
+              "ivf_pq4_scan: out must be a flat contiguous fp32 GPU tensor");
+  const unsigned int* fw = nullptr;
+  if (filter_words.has_value()) {
+    const torch::Tensor& f = filter_words.value();
+    TORCH_CHECK(f.is_cuda() && f.scalar_type() == torch::kInt32 && f.is_contiguous() &&
+                f.dim() == 1 && filter_bits >= 0 && f.numel() * 32 >= filter_bits,
+                "ivf_pq4_scan: filter must be int32 words covering filter_bits");
+    fw = reinterpret_cast<const unsigned int*>(f.data_ptr<int>());
+  }
+  raft_amd::launch_ivf_pq4_scan(
+      codes.data_ptr<uint8_t>(), lo, idx, queries.data_ptr<float>(),
+      centroids.data_ptr<float>(), codebooks.data_ptr<float>(), il, ib, ic, ni, pq, po, fw,
+      filter_bits, out.data_ptr<float>(), out.numel(), n_lists, total_rows, queries.size(0),
+      n_pairs, max_items, (int)d, pq_dim, pq_len, (int)metric, (int)qg, (int)y_split,
+      cur_stream());
 }
 
 // refine: the k best of every query's candidate rows by exact fp32 distance.
@@ -2085,6 +2186,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("probes"), pybind11::arg("pair_out_off"),
         pybind11::arg("filter_words"), pybind11::arg("filter_bits"), pybind11::arg("out"),
         pybind11::arg("metric"), pybind11::arg("y_split"));
+  m.def("ivf_pq4_encode", &ivf_pq4_encode,
+        "IVF-PQ, 4-bit codes: nearest codebook entry per subspace, two codes per byte",
+        pybind11::arg("x"), pybind11::arg("labels"), pybind11::arg("centroids"),
+        pybind11::arg("codebooks"), pybind11::arg("codes"));
+  m.def("ivf_pq4_scan", &ivf_pq4_scan,
+        "IVF-PQ, 4-bit codes: list-major LUT scan into a ragged candidate buffer",
+        pybind11::arg("codes"), pybind11::arg("list_offsets"), pybind11::arg("indices"),
+        pybind11::arg("queries"), pybind11::arg("centroids"), pybind11::arg("codebooks"),
+        pybind11::arg("item_list"), pybind11::arg("item_pair_begin"),
+        pybind11::arg("item_pair_count"), pybind11::arg("n_items"),
+        pybind11::arg("pair_query"), pybind11::arg("pair_out_off"),
+        pybind11::arg("filter_words"), pybind11::arg("filter_bits"), pybind11::arg("out"),
+        pybind11::arg("metric"), pybind11::arg("qg"), pybind11::arg("y_split"));
+  m.def("ivf_pq4_scan_max_qg", [](int64_t pq_dim, int64_t pq_len) {
+    TORCH_CHECK(pq_dim >= 1 && pq_len >= 1 && pq_dim <= 2147483647ll &&
+                pq_len <= 2147483647ll, "ivf_pq4_scan_max_qg: pq_dim and pq_len must be positive");
+    return (int64_t)raft_amd::ivf_pq4_scan_max_qg((int)pq_dim, (int)pq_len);
+  }, "largest query-group size (8, 4, 2 or 1) whose tables and residuals fit the 4-bit "
+     "scan's 64 KiB of LDS; 0 if the kernels do not serve the shape",
+        pybind11::arg("pq_dim"), pybind11::arg("pq_len"));
   m.def("refine_topk", &refine_topk,
         "exact re-rank of kNN candidates: gather, fp32 distance and top-k in one kernel",
         pybind11::arg("dataset"), pybind11::arg("queries"), pybind11::arg("candidates"),

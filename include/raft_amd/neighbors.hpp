@@ -168,6 +168,38 @@ void launch_ivf_pq_scan(const unsigned char* codes, const long long* list_offset
                         long long n_queries, int n_probes, int d, int pq_dim, int pq_len,
                         int metric, int y_split, hipStream_t s);
 
+// IVF-PQ with 4-bit codes (csrc/ivf_pq4.hip). codebooks is fp32
+// [pq_dim][pq_len][16]; a stored row is row_bytes = ceil(pq_dim / 2) rounded
+// up to 16 bytes, byte t holding subspace 2t in bits 0..3 and subspace 2t + 1
+// in bits 4..7, pad nibbles and pad bytes 0.
+//
+// Encode: codes[n][row_bytes] (row-major, 16-byte aligned) by the rule of
+// launch_ivf_pq_encode; a row whose label is outside [0, n_lists) gets zeros.
+// pq_len <= 32.
+void launch_ivf_pq4_encode(const float* x, const long long* labels, const float* centroids,
+                           const float* codebooks, unsigned char* codes, long long n,
+                           long long n_lists, int d, int pq_dim, int pq_len, hipStream_t s);
+// Scan, list-major: the work items, pair arrays, list_offsets / indices /
+// filter / out / metric of launch_ivf_flat_scan over the interleaved code
+// buffer (row_bytes / 16 chunks of 32 subspaces, 16-byte aligned). A block
+// holds the fp32 look-up tables and residuals of qg queries:
+// qg * (2048 * row_bytes / 16 + 4 * pq_dim * pq_len) bytes plus 16 + 4 qg
+// within 64 KiB. ivf_pq4_scan_max_qg is the largest qg in {8, 4, 2, 1} that
+// fits, 0 for pq_dim > 256 or pq_len > 32; a larger qg makes the launcher
+// throw. Distances are to the reconstructed rows and do not depend on qg.
+int ivf_pq4_scan_max_qg(int pq_dim, int pq_len);
+void launch_ivf_pq4_scan(const unsigned char* codes, const long long* list_offsets,
+                         const long long* indices, const float* queries,
+                         const float* centroids, const float* codebooks,
+                         const long long* item_list, const long long* item_pair_begin,
+                         const long long* item_pair_count, const long long* n_items,
+                         const long long* pair_query, const long long* pair_out_off,
+                         const unsigned int* filter_words, long long filter_bits, float* out,
+                         long long out_numel, long long n_lists, long long total_rows,
+                         long long n_queries, long long n_pairs, long long max_items, int d,
+                         int pq_dim, int pq_len, int metric, int qg, int y_split,
+                         hipStream_t s);
+
 // refine (csrc/refine.hip): exact re-rank of kNN candidates, one block per
 // query. dataset is [n][d] of dtype 0 fp32, 1 bf16 or 2 fp16 with rows
 // row_pitch ELEMENTS apart (n < 2^32 - 1); queries fp32 [n_queries][d];

@@ -342,14 +342,17 @@ def _chunk_layout(index, probes):
     return row_off, row_off[:-1, None] + (ends - plen)
 
 
-def _scan_kernel(index, q32, probes, pair_off, cand, fwords, fbits, qg):
-    """List-major scan of one query chunk on the GPU (no host sync). q32 is
-    fp32, or the index's dtype for an int8 / uint8 index."""
-    ext = require_ext()
-    dev = q32.device
+def _scan_items(probes, pair_off, n_lists, qg):
+    """The work items of a list-major scan (this module's and IVF-PQ's 4-bit
+    one), built on the device: the (query, probe) pairs sorted by list (stable)
+    and cut into groups of at most qg. Returns (il, begin, count, n_items,
+    pair_query, pair_out_off): per item its list, first sorted pair and pair
+    count; the device scalar [1] that says how many of the il.numel() items
+    are real (the host knows only that bound); per sorted pair its query row
+    and the offset of its list segment in the candidate buffer."""
+    dev = probes.device
     qc, n_probes = probes.shape
     n_pairs = qc * n_probes
-    n_lists = index.n_lists
     flat = probes.reshape(-1)
     _, order = torch.sort(flat, stable=True)
     pair_query = order // n_probes
@@ -364,10 +367,18 @@ def _scan_kernel(index, q32, probes, pair_off, cand, fwords, fbits, qg):
     j = i - (gend - groups)[il]
     begin = (cnt.cumsum(0) - cnt)[il] + j * qg
     count = (cnt[il] - j * qg).clamp_(max=qg)
-    y_split = max(1, min(-(-_TARGET_BLOCKS // max_items), index.max_list_pad // _GROUP))
-    ext.ivf_flat_scan(index.data, index.list_offsets, index.indices, q32, il, begin,
-                      count, gend[-1:].contiguous(), pair_query, pair_out_off, fwords,
-                      fbits, cand, _METRIC_CODES[index.metric], qg, y_split)
+    return il, begin, count, gend[-1:].contiguous(), pair_query, pair_out_off
+
+
+def _scan_kernel(index, q32, probes, pair_off, cand, fwords, fbits, qg):
+    """List-major scan of one query chunk on the GPU (no host sync). q32 is
+    fp32, or the index's dtype for an int8 / uint8 index."""
+    il, begin, count, n_items, pair_query, pair_out_off = _scan_items(
+        probes, pair_off, index.n_lists, qg)
+    y_split = max(1, min(-(-_TARGET_BLOCKS // il.numel()), index.max_list_pad // _GROUP))
+    require_ext().ivf_flat_scan(index.data, index.list_offsets, index.indices, q32, il, begin,
+                                count, n_items, pair_query, pair_out_off, fwords,
+                                fbits, cand, _METRIC_CODES[index.metric], qg, y_split)
 
 
 def _scan_torch(index, q32, probes, pair_off, cand, fdense, bad):

@@ -1,39 +1,50 @@
 """IVF-PQ: an inverted-file index over product-quantised residuals.
 
 Reference parity: the historical raft::neighbors::ivf_pq::{build, extend,
-search, serialize} with 8-bit codes and per-subspace codebooks. The data set is
-partitioned like IVF-Flat; a row is stored as pq_dim bytes: its residual to the
-list centroid is cut into pq_dim sub-vectors of pq_len = ceil(d / pq_dim)
+search, serialize} with per-subspace codebooks and pq_bits = 8 or 4. The data
+set is partitioned like IVF-Flat; a row is stored as pq_dim codes: its residual
+to the list centroid is cut into pq_dim sub-vectors of pq_len = ceil(d / pq_dim)
 features (d_rot = pq_dim * pq_len, features past d are zero) and every
-sub-vector is replaced by the number of its nearest entry among the 256 of that
-subspace's codebook. A row costs pq_dim bytes instead of 4 * d, and a search
-scores it with pq_dim table look-ups instead of d FMAs.
+sub-vector is replaced by the number of its nearest entry among the book_size =
+2^pq_bits (256 or 16) of that subspace's codebook. A row costs pq_dim bytes (half
+that with 4-bit codes) instead of 4 * d, and a search scores it with pq_dim
+table look-ups instead of d FMAs.
 
 Distances are ASYMMETRIC (ADC): from the exact query to the RECONSTRUCTED row
 centroid + decoded residual, not to the original vector. ivf_pq_search(...,
 dataset=x, refine_ratio=r) re-ranks k * r such candidates against the original
 vectors with neighbors.refine and returns exact distances.
 
-Storage is the IVF-Flat layout (neighbors/ivf_flat.py) with uint8 elements:
-16 codes per 16-byte chunk, pq_dim_pad = pq_dim rounded up to 16 with zero pad
-bytes, lists padded to 64 rows, byte (group g, chunk j, row r, b) at
+Storage is the IVF-Flat layout (neighbors/ivf_flat.py) with uint8 elements: a
+stored row is row_bytes bytes, lists are padded to 64 rows, byte (group g,
+chunk j, row r, b) at
 
-    ((g * (pq_dim_pad / 16) + j) * 64 + r) * 16 + b.
+    ((g * (row_bytes / 16) + j) * 64 + r) * 16 + b.
 
-Codebooks are fp32 [pq_dim, pq_len, 256], entry-minor, which the kernels read
-coalesced.
+8-bit codes: byte t of a row is the code of subspace t; row_bytes = pq_dim_pad =
+pq_dim rounded up to 16 with zero pad bytes, 16 subspaces per 16-byte chunk.
+4-bit codes: byte t of a row holds subspace 2t in bits 0..3 and subspace 2t + 1
+in bits 4..7; the pad nibble of an odd pq_dim is 0; row_bytes = ceil(pq_dim / 2)
+rounded up to 16 with zero pad bytes, 32 subspaces per chunk.
+
+Codebooks are fp32 [pq_dim, pq_len, book_size], entry-minor, which the kernels
+read coalesced. unpack_list returns one code per byte for either width.
 
 MI355X design (csrc/ivf_pq.hip): ivf_pq_encode forms the residual sub-vector in
 registers and walks a subspace's codebook staged in LDS; ivf_pq_scan is
 PAIR-major: one block per (query, probe) pair builds the pair's full fp32
 look-up table in LDS (up to 128 KiB of CDNA4's 160 KiB) and gathers from it
 with lane = row. Candidates go to the ragged buffer of IVF-Flat and the same
-select and id mapping finish the search.
+select and id mapping finish the search. 4-bit codes have kernels of their own
+(csrc/ivf_pq4.hip): a 16-entry table row is 64 bytes, so ivf_pq4_scan is
+LIST-major like the flat scan: a block holds the tables of up to 8 queries
+that probe one list (within 64 KiB of LDS) and reads the list's codes once for
+all of them; ivf_pq4_encode writes one packed 16-byte chunk per thread.
 
 CPU tensors run the same algorithm in plain torch (a cdist argmin per subspace
-to encode, table plus gather to scan). A GPU index with pq_dim > 128 or
-pq_len > 32 takes that torch path on the GPU (the select is still native). A
-GPU call without the native extension raises.
+to encode, table plus gather to scan). A GPU index with pq_len > 32, or with
+pq_dim > 128 (8-bit) or pq_dim > 256 (4-bit), takes that torch path on the GPU
+(the select is still native). A GPU call without the native extension raises.
 """
 from __future__ import annotations
 
@@ -50,25 +61,29 @@ from raft_amd.matrix.select_k import select_k
 from raft_amd.utils import row_chunks
 
 from .ivf_flat import (_GROUP, _METRIC_CODES, _TARGET_BLOCKS, _check_vectors, _chunk_layout,
-                       _filter_parts, _finish, _pack, _resolve_metric, _select)
+                       _filter_parts, _finish, _pack, _resolve_metric, _scan_items, _select)
 
-_BOOK = 256                 # 8-bit codes
-_CHUNK = 16                 # codes in one 16-byte chunk
+_BOOKS = {8: 256, 4: 16}    # pq_bits -> entries of one codebook
+_CHUNK = 16                 # bytes in one chunk
 #: the shapes csrc/ivf_pq.hip serves: a 128 KiB table, a 32-register residual
 _MAX_KERNEL_PQ_DIM = 128
 _MAX_KERNEL_PQ_LEN = 32
+#: the shapes csrc/ivf_pq4.hip serves (and ext.ivf_pq4_scan_max_qg admits)
+_MAX_KERNEL_PQ4_DIM = 256
 _MAGIC = b"RAFTAMD_IVFPQ\x00\x00\x00"
-_VERSION = 1
+_VERSION = 1                # 8-bit codes; a 4-bit index is written as version 2
+_VERSION_PQ4 = 2
 _HEADER = "<16s6q16s"
 
 
 @dataclass
 class IvfPqParams:
     """Build parameters (reference ivf_pq::index_params); the first seven are
-    IvfFlatParams'. pq_dim: subspaces = bytes per row, any value in [1, d];
+    IvfFlatParams'. pq_dim: subspaces = codes per row, any value in [1, d];
     0 means ceil(d / 2) rounded up to a multiple of 16, capped at 128 and at d.
+    pq_bits: 8 or 4, the bits of one code; a codebook has 2^pq_bits entries.
     Every codebook is one kmeans_fit of pq_kmeans_n_iters iterations on at
-    most 256 * max_train_points_per_pq_code residuals."""
+    most 2^pq_bits * max_train_points_per_pq_code residuals."""
     n_lists: int = 1024
     metric: DistanceType | str = "sqeuclidean"
     kmeans_n_iters: int = 20
@@ -79,12 +94,14 @@ class IvfPqParams:
     pq_dim: int = 0
     pq_kmeans_n_iters: int = 25
     max_train_points_per_pq_code: int = 256
+    pq_bits: int = 8
 
 
 class IvfPqIndex:
-    """The index: centroids [n_lists, d] fp32, codebooks [pq_dim, pq_len, 256]
-    fp32, list_offsets / list_sizes / indices as in IvfFlatIndex, codes (the
-    flat interleaved uint8 buffer), metric, dim, pq_dim, n_rows, fp32_mode."""
+    """The index: centroids [n_lists, d] fp32, codebooks [pq_dim, pq_len,
+    book_size] fp32 (book_size 256: pq_bits 8; 16: pq_bits 4), list_offsets /
+    list_sizes / indices as in IvfFlatIndex, codes (the flat interleaved uint8
+    buffer, row_bytes per row), metric, dim, pq_dim, n_rows, fp32_mode."""
 
     def __init__(self, centroids, codebooks, list_offsets, list_sizes, codes, indices,
                  metric, dim, n_rows, fp32_mode="auto"):
@@ -98,6 +115,8 @@ class IvfPqIndex:
         self.dim = int(dim)
         self.pq_dim = int(codebooks.shape[0])
         self.pq_len = int(codebooks.shape[1])
+        self.book_size = int(codebooks.shape[2])
+        self.pq_bits = _pq_bits_of(self.book_size)
         self.n_rows = int(n_rows)
         self.fp32_mode = fp32_mode
         padded = list_offsets[1:] - list_offsets[:-1]
@@ -121,10 +140,20 @@ class IvfPqIndex:
         return -(-self.pq_dim // _CHUNK) * _CHUNK
 
     @property
+    def row_bytes(self) -> int:
+        """Padded bytes of one stored row."""
+        return _row_bytes(self.pq_dim, self.pq_bits)
+
+    @property
     def kernels_serve(self) -> bool:
-        """Whether csrc/ivf_pq.hip encodes and scans this shape on the GPU."""
-        return (self.device.type == "cuda" and self.pq_dim <= _MAX_KERNEL_PQ_DIM
-                and self.pq_len <= _MAX_KERNEL_PQ_LEN)
+        """Whether csrc/ivf_pq.hip (8-bit) or csrc/ivf_pq4.hip (4-bit) encodes
+        and scans this shape on the GPU."""
+        if self.device.type != "cuda" or self.pq_len > _MAX_KERNEL_PQ_LEN:
+            return False
+        if self.pq_bits == 8:
+            return self.pq_dim <= _MAX_KERNEL_PQ_DIM
+        return (self.pq_dim <= _MAX_KERNEL_PQ4_DIM
+                and require_ext().ivf_pq4_scan_max_qg(self.pq_dim, self.pq_len) >= 1)
 
     def to(self, device) -> "IvfPqIndex":
         return IvfPqIndex(self.centroids.to(device), self.codebooks.to(device),
@@ -133,9 +162,9 @@ class IvfPqIndex:
                           self.dim, self.n_rows, self.fp32_mode)
 
     def _padded_codes(self) -> torch.Tensor:
-        """All padded rows' codes [total, pq_dim_pad] in slot order."""
+        """All padded rows' stored bytes [total, row_bytes] in slot order."""
         total = self.indices.numel()
-        pp = self.pq_dim_pad
+        pp = self.row_bytes
         rows = self.codes.view(total // _GROUP, pp // _CHUNK, _GROUP, _CHUNK)
         return rows.permute(0, 2, 1, 3).reshape(total, pp)
 
@@ -143,11 +172,12 @@ class IvfPqIndex:
         """The codes [size, pq_dim] uint8 and dataset ids [size] of list l."""
         r0 = int(self.list_offsets[l])
         size = int(self.list_sizes[l])
-        g = self.codes.view(-1, self.pq_dim_pad // _CHUNK, _GROUP, _CHUNK)
+        g = self.codes.view(-1, self.row_bytes // _CHUNK, _GROUP, _CHUNK)
         g = g[r0 // _GROUP:(r0 + size + _GROUP - 1) // _GROUP]
-        rows = g.permute(0, 2, 1, 3).reshape(g.shape[0] * _GROUP, self.pq_dim_pad)
-        rows = rows[:size, :self.pq_dim]
-        return rows.contiguous(), self.indices[r0:r0 + size]
+        rows = g.permute(0, 2, 1, 3).reshape(g.shape[0] * _GROUP, self.row_bytes)[:size]
+        if self.pq_bits == 4:
+            rows = torch.stack([rows & 15, rows >> 4], dim=2).reshape(size, 2 * self.row_bytes)
+        return rows[:, :self.pq_dim].contiguous(), self.indices[r0:r0 + size]
 
     def reconstruct_list(self, l: int):
         """The reconstructed rows [size, d] fp32 (centroid + decoded residual)
@@ -157,6 +187,18 @@ class IvfPqIndex:
         dec = self.codebooks.permute(0, 2, 1)[s, codes.long()]   # [size, pq_dim, pq_len]
         rows = dec.reshape(codes.shape[0], self.d_rot)[:, :self.dim]
         return rows + self.centroids[l], ids
+
+
+def _pq_bits_of(book_size: int) -> int:
+    for bits, book in _BOOKS.items():
+        if book == book_size:
+            return bits
+    raise ValueError(f"a codebook has 16 (pq_bits 4) or 256 (pq_bits 8) entries, got "
+                     f"{book_size}")
+
+
+def _row_bytes(pq_dim: int, pq_bits: int) -> int:
+    return -(-(pq_dim * pq_bits) // (8 * _CHUNK)) * _CHUNK
 
 
 def _default_pq_dim(d: int) -> int:
@@ -173,44 +215,49 @@ def _subspaces(v, pq_dim, pq_len):
 
 
 def _encode(x32, labels, centroids, codebooks, use_kernel):
-    """codes [n, pq_dim_pad] uint8 (pad bytes 0): per subspace the entry
-    nearest to x - centroids[labels]; exact ties go to the smallest entry."""
+    """The stored rows [n, row_bytes] uint8 (pad nibbles and bytes 0): per
+    subspace the entry nearest to x - centroids[labels]; exact ties go to the
+    smallest entry."""
     n = x32.shape[0]
-    pq_dim, pq_len = codebooks.shape[0], codebooks.shape[1]
-    pq_dim_pad = -(-pq_dim // _CHUNK) * _CHUNK
+    pq_dim, pq_len, book = codebooks.shape
+    pq_bits = _pq_bits_of(book)
+    row_bytes = _row_bytes(pq_dim, pq_bits)
     if use_kernel:
-        codes = torch.empty((n, pq_dim_pad), dtype=torch.uint8, device=x32.device)
-        require_ext().ivf_pq_encode(x32.contiguous(), labels.contiguous(), centroids,
-                                    codebooks, codes)
+        codes = torch.empty((n, row_bytes), dtype=torch.uint8, device=x32.device)
+        encode = require_ext().ivf_pq_encode if pq_bits == 8 else require_ext().ivf_pq4_encode
+        encode(x32.contiguous(), labels.contiguous(), centroids, codebooks, codes)
         return codes
-    codes = torch.zeros((n, pq_dim_pad), dtype=torch.uint8, device=x32.device)
-    books = codebooks.permute(0, 2, 1).contiguous()                # [pq_dim, 256, pq_len]
-    for s0, s1 in row_chunks(n, max(1, (1 << 24) // (_BOOK * pq_dim))):
+    # one code per byte, an even count, then two to a byte for 4-bit codes
+    codes = torch.zeros((n, row_bytes * (8 // pq_bits)), dtype=torch.uint8, device=x32.device)
+    books = codebooks.permute(0, 2, 1).contiguous()                # [pq_dim, book, pq_len]
+    for s0, s1 in row_chunks(n, max(1, (1 << 24) // (book * pq_dim))):
         r = _subspaces(x32[s0:s1] - centroids[labels[s0:s1]], pq_dim, pq_len)
         dist = torch.cdist(r.permute(1, 0, 2).contiguous(), books,
                            compute_mode="donot_use_mm_for_euclid_dist")
         codes[s0:s1, :pq_dim] = dist.argmin(dim=2).t().to(torch.uint8)
+    if pq_bits == 4:
+        codes = codes[:, 0::2] | (codes[:, 1::2] << 4)
     return codes
 
 
-def _train_codebooks(x32, centroids, params, pq_dim, pq_len):
-    """One 256-cluster kmeans_fit per subspace on the residuals of a seeded
-    sample (always L2 residuals, also for InnerProduct)."""
+def _train_codebooks(x32, centroids, params, pq_dim, pq_len, book):
+    """One kmeans_fit with book clusters per subspace on the residuals of a
+    seeded sample (always L2 residuals, also for InnerProduct)."""
     from raft_amd.cluster.kmeans import KMeansParams, kmeans_fit, kmeans_predict
     n = x32.shape[0]
-    n_train = min(n, _BOOK * int(params.max_train_points_per_pq_code))
-    if n_train < _BOOK:
-        raise ValueError(f"codebook training needs at least {_BOOK} rows, got {n_train}")
+    n_train = min(n, book * int(params.max_train_points_per_pq_code))
+    if n_train < book:
+        raise ValueError(f"codebook training needs at least {book} rows, got {n_train}")
     if n_train < n:
         # drawn on the host so that a CPU and a GPU build train on the same rows
         pick = torch.randperm(n, generator=torch.Generator().manual_seed(params.seed))
         x32 = x32[pick[:n_train].to(x32.device)]
     labels = kmeans_predict(centroids, x32, fp32_mode=params.fp32_mode).to(torch.int64)
     res = _subspaces(x32 - centroids[labels], pq_dim, pq_len)
-    books = torch.empty((pq_dim, pq_len, _BOOK), dtype=torch.float32, device=x32.device)
+    books = torch.empty((pq_dim, pq_len, book), dtype=torch.float32, device=x32.device)
     for s in range(pq_dim):
         model = kmeans_fit(res[:, s].contiguous(),
-                           KMeansParams(n_clusters=_BOOK, max_iter=params.pq_kmeans_n_iters,
+                           KMeansParams(n_clusters=book, max_iter=params.pq_kmeans_n_iters,
                                         seed=params.seed + 7919 * (s + 1), init="random",
                                         fp32_mode=params.fp32_mode))
         books[s] = model.centroids.t()
@@ -224,16 +271,23 @@ def ivf_pq_build(x: torch.Tensor, params: IvfPqParams | None = None, *,
 
     x is fp32, bf16 or fp16 and is widened to fp32. The coarse centroids are
     trained as in ivf_flat_build. The codebooks are trained on the residuals
-    of a seeded sample of at most 256 * params.max_train_points_per_pq_code
-    rows: per subspace one kmeans_fit with 256 clusters, seeded from
-    params.seed and the subspace number, always on L2 residuals (also for
-    InnerProduct). centroids= [n_lists, d] and codebooks= [pq_dim, pq_len, 256]
-    skip the respective training; codebooks= overrides params.pq_dim.
+    of a seeded sample of at most book_size * params.max_train_points_per_pq_code
+    rows (book_size = 2^params.pq_bits, 256 or 16): per subspace one kmeans_fit
+    with book_size clusters, seeded from params.seed and the subspace number,
+    always on L2 residuals (also for InnerProduct). centroids= [n_lists, d] and
+    codebooks= [pq_dim, pq_len, 256 or 16] skip the respective training;
+    codebooks= overrides params.pq_dim and, by its last extent, params.pq_bits.
     params.add_data_on_build=False returns an index with empty lists.
     """
     from raft_amd.cluster.kmeans import kmeans_balanced_fit
     params = params if params is not None else IvfPqParams()
     metric = _resolve_metric(params.metric)
+    if int(params.pq_bits) not in _BOOKS:
+        raise ValueError(f"pq_bits must be 4 or 8, got {params.pq_bits}")
+    book = _BOOKS[int(params.pq_bits)]
+    if codebooks is not None and codebooks.dim() == 3:
+        book = int(codebooks.shape[2])
+        _pq_bits_of(book)
     x32 = _check_vectors(x, "x").float()
     n, d = x32.shape
     if d < 1:
@@ -256,9 +310,9 @@ def ivf_pq_build(x: torch.Tensor, params: IvfPqParams | None = None, *,
     dev = x32.device
     centroids = centroids.to(dev, torch.float32).contiguous()
     if codebooks is None:
-        codebooks = _train_codebooks(x32, centroids, params, pq_dim, pq_len)
-    elif tuple(codebooks.shape) != (pq_dim, pq_len, _BOOK):
-        raise ValueError(f"codebooks must be [pq_dim, {pq_len}, {_BOOK}] with pq_dim in "
+        codebooks = _train_codebooks(x32, centroids, params, pq_dim, pq_len, book)
+    elif tuple(codebooks.shape) != (pq_dim, pq_len, book):
+        raise ValueError(f"codebooks must be [pq_dim, {pq_len}, 16 or 256] with pq_dim in "
                          f"[1, {d}], got {tuple(codebooks.shape)}")
     codebooks = codebooks.to(dev, torch.float32).contiguous()
     n_lists = centroids.shape[0]
@@ -307,7 +361,7 @@ def ivf_pq_extend(index: IvfPqIndex, new_vectors: torch.Tensor,
         new_indices = torch.cat([index.indices[keep], new_indices])
         labels = torch.cat([slot_list, labels])   # stable sort: old rows first
     offsets, sizes, data, indices = _pack(codes, new_indices, labels, index.n_lists,
-                                          index.pq_dim_pad)
+                                          index.row_bytes)
     return IvfPqIndex(index.centroids, index.codebooks, offsets, sizes, data, indices,
                       index.metric, index.dim, index.n_rows + m, index.fp32_mode)
 
@@ -324,12 +378,27 @@ def _scan_kernel(index, q32, probes, pair_off, cand, fwords, fbits):
                               _METRIC_CODES[index.metric], y_split)
 
 
+def _scan_kernel4(index, q32, probes, pair_off, cand, fwords, fbits):
+    """List-major LUT scan of one query chunk of a 4-bit index (no host sync):
+    the work items of the flat scan, the group size from the LDS budget."""
+    ext = require_ext()
+    qg = ext.ivf_pq4_scan_max_qg(index.pq_dim, index.pq_len)
+    il, begin, count, n_items, pair_query, pair_out_off = _scan_items(
+        probes, pair_off, index.n_lists, qg)
+    # a block's four waves take one 64-row group each
+    y_split = max(1, min(-(-_TARGET_BLOCKS // il.numel()),
+                         -(-index.max_list_pad // (4 * _GROUP))))
+    ext.ivf_pq4_scan(index.codes, index.list_offsets, index.indices, q32, index.centroids,
+                     index.codebooks, il, begin, count, n_items, pair_query, pair_out_off,
+                     fwords, fbits, cand, _METRIC_CODES[index.metric], qg, y_split)
+
+
 def _scan_torch(index, q32, probes, pair_off, cand, fdense, bad):
     """The same candidate buffer with torch ops: table, then gather."""
     dev = q32.device
     cand.fill_(bad)
     ip = index.metric == DistanceType.InnerProduct
-    books = index.codebooks.unsqueeze(0)                   # [1, pq_dim, pq_len, 256]
+    books = index.codebooks.unsqueeze(0)                   # [1, pq_dim, pq_len, book]
     for l in torch.unique(probes).tolist():
         codes, ids = index.unpack_list(l)
         size = codes.shape[0]
@@ -342,12 +411,12 @@ def _scan_torch(index, q32, probes, pair_off, cand, fdense, bad):
         qi, pi = (probes == l).nonzero(as_tuple=True)
         cols = torch.arange(size, device=dev)
         c = index.centroids[l]
-        sub = max(1, (1 << 22) // (_BOOK * index.d_rot + size * index.pq_dim))
+        sub = max(1, (1 << 22) // (index.book_size * index.d_rot + size * index.pq_dim))
         for s0, s1 in row_chunks(qi.numel(), sub):
             qv = q32[qi[s0:s1]]
             if ip:
                 r = _subspaces(qv, index.pq_dim, index.pq_len).unsqueeze(3)
-                lut = (r * books).sum(dim=2)               # [nq, pq_dim, 256]
+                lut = (r * books).sum(dim=2)               # [nq, pq_dim, book]
             else:
                 r = _subspaces(qv - c, index.pq_dim, index.pq_len).unsqueeze(3)
                 lut = ((r - books) ** 2).sum(dim=2)
@@ -453,7 +522,8 @@ def ivf_pq_search(index: IvfPqIndex, queries: torch.Tensor, k: int, n_probes: in
             cand = ws.view(((s1 - s0) * n_probes * index.max_list_pad,), torch.float32)
             row_off, pair_off = _chunk_layout(index, pc)
             if use_kernel:
-                _scan_kernel(index, q32[s0:s1], pc, pair_off, cand, fwords, fbits)
+                scan = _scan_kernel if index.pq_bits == 8 else _scan_kernel4
+                scan(index, q32[s0:s1], pc, pair_off, cand, fwords, fbits)
             else:
                 _scan_torch(index, q32[s0:s1], pc, pair_off, cand, fdense, bad)
             vals, pos = _select(cand, row_off, k, select_min, bad)
@@ -468,9 +538,11 @@ def ivf_pq_save(index: IvfPqIndex, path: str) -> None:
     """Write the index to one file (reference ivf_pq::serialize): a header
     (magic, version, metric, dim, n_rows, pq_dim, n_lists, fp32_mode), then
     centroids, codebooks, list_offsets, list_sizes, codes and indices as .npy
-    records."""
+    records. An 8-bit index is version 1, a 4-bit index version 2; the book
+    size is the codebooks' last extent."""
     with open(path, "wb") as f:
-        f.write(struct.pack(_HEADER, _MAGIC, _VERSION, _METRIC_CODES[index.metric],
+        version = _VERSION if index.pq_bits == 8 else _VERSION_PQ4
+        f.write(struct.pack(_HEADER, _MAGIC, version, _METRIC_CODES[index.metric],
                             index.dim, index.n_rows, index.pq_dim, index.n_lists,
                             index.fp32_mode.encode("ascii")))
         for t in (index.centroids, index.codebooks, index.list_offsets, index.list_sizes,
@@ -485,13 +557,14 @@ def ivf_pq_load(path: str, device=None) -> IvfPqIndex:
         if len(raw) != struct.calcsize(_HEADER) or raw[:16] != _MAGIC:
             raise ValueError(f"{path} is not an IVF-PQ index file")
         _, version, metric, dim, n_rows, pq_dim, n_lists, mode = struct.unpack(_HEADER, raw)
-        if version != _VERSION:
+        if version not in (_VERSION, _VERSION_PQ4):
             raise ValueError(f"{path}: unsupported IVF-PQ file version {version}")
         centroids, codebooks, offsets, sizes, codes, indices = (
             deserialize_mdspan(f, device=device) for _ in range(6))
     metrics = {c: m for m, c in _METRIC_CODES.items()}
     if (metric not in metrics or centroids.shape[0] != n_lists or codebooks.dim() != 3
-            or codebooks.shape[0] != pq_dim):
+            or codebooks.shape[0] != pq_dim or codebooks.shape[2] not in _BOOKS.values()
+            or (version == _VERSION and codebooks.shape[2] != _BOOKS[8])):
         raise ValueError(f"{path}: corrupt IVF-PQ header")
     return IvfPqIndex(centroids, codebooks, offsets, sizes, codes, indices, metrics[metric],
                       dim, n_rows, mode.rstrip(b"\x00").decode("ascii"))
